@@ -14,7 +14,11 @@ compute stream waited for the last bucket.  `eager_reference_loop` is what the r
 package (eager launches, torch mirror of core/Loss.py, foreach Adam) -- measured next to the headline so that the cost of not
 adopting the three-line TrainStep patch is visible.
 
-Prints ONE JSON line (rank 0).  `roofline`: the GEMM/implicit-conv kernel family (rih_gemm), timed live with HIP events
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps and prints it; `eager_reference_loop`,
+the three rooflines and `cpu_baseline` are measured with `--full` only (null otherwise).  `--dump-outputs DIR` writes what the
+last timed step computed as .npy files, for output-for-output comparisons of two builds (the inputs are seeded).
+
+`roofline`: the GEMM/implicit-conv kernel family (rih_gemm), timed live with HIP events
 on the launch stream; achieved = SURVEY 8d algorithmic FLOPs (53.2 GFLOP/img fwd+bwd) x images per step / GEMM-family
 time per step (`achieved_launched` = the FLOPs actually launched: dead branches are skipped).  `roofline_hbm`: the BatchNorm
 kernel family (largest HBM-bound group) the same way in GB/s against 8 TB/s; `roofline_mano`: the MANO layer micro-benchmark
@@ -165,6 +169,51 @@ def mano_roofline(device, hands=4096, iters=20):
             'fwdbwd_us': r['fwdbwd_us'], 'fwdbwd_hands_per_s': r['fwdbwd_hands_per_s']}
 
 
+DUMP_BUDGET_BYTES = 64 << 20       # --dump-outputs: all files together
+DUMP_PER_TENSOR = 8192             # elements kept of each larger tensor (a fixed sample, seeded by the tensor's name)
+
+
+def _sample(name, t):
+    """Flattened float32 copy of `t`, or of DUMP_PER_TENSOR of its elements at positions drawn from a generator seeded with
+    the tensor's name: the same positions in every run and every build."""
+    import zlib
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_PER_TENSOR:
+        g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+        idx = torch.randint(flat.numel(), (DUMP_PER_TENSOR,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu()
+
+
+def dump_outputs(outdir, arrays):
+    """Write every (name, tensor) of `arrays` as <outdir>/<name>.npy: float64 stays float64, everything else is float32."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    conv = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        conv[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit('--dump-outputs: %d bytes exceed the %d-byte budget' % (total, DUMP_BUDGET_BYTES))
+    for name, a in conv.items():
+        np.save(os.path.join(outdir, name + '.npy'), a)
+    print('[bench] wrote %d arrays (%.1f MB) to %s' % (len(conv), total / 1e6, outdir), file=sys.stderr, flush=True)
+
+
+def training_outputs(model, loss):
+    """What the training step hands its caller after the last timed step: the loss, the updated parameters, the gradients
+    the step computed and the BatchNorm running statistics it updated (larger tensors as a fixed sample, see _sample).
+    Concatenated in named_parameters / named_buffers order."""
+    params = [(n, p) for n, p in model.named_parameters()]
+    grads = [(n, p.grad) for n, p in params if p.grad is not None]
+    stats = [(n, b) for n, b in model.named_buffers() if 'running' in n and b.is_floating_point()]
+    return {'loss': loss.detach().reshape(1),
+            'params': torch.cat([_sample(n, p) for n, p in params]),
+            'grads': torch.cat([_sample(n, g) for n, g in grads]),
+            'bn_running_stats': torch.cat([_sample(n, b) for n, b in stats])}
+
+
 _REAL_STDOUT = None
 
 
@@ -277,6 +326,13 @@ def config5(args):
         g.replay()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if args.dump_outputs:
+        from renderih_amd import testing
+        out, hands = keep
+        arrays = {k.replace('.', '_'): _sample(k, v) for k, v in testing.flatten_outputs(out).items() if torch.is_tensor(v)}
+        for s_, (v_, j_) in zip(('left', 'right'), hands):
+            arrays['mano_verts_' + s_], arrays['mano_joints_' + s_] = _sample('mano.v.' + s_, v_), _sample('mano.j.' + s_, j_)
+        dump_outputs(args.dump_outputs, arrays)
     del keep
     emit({'metric': 'images/sec inference (encoder + attention decoder + MANO layer), batch 256 fp16, hipGraph',
                       'value': round(B * args.steps / el, 2), 'unit': 'images/sec', 'n_gpus': 1, 'steps': args.steps,
@@ -320,10 +376,21 @@ def main():
                          'backward then groups its weight gradients into four launches instead of twelve: +1.2 %% same-box)')
     ap.add_argument('--no-overlap', action='store_true', help='all-reduce on the compute stream (no overlap with backward)')
     ap.add_argument('--no-reference-loop', action='store_true', help="skip the 5-step measurement of the reference's unmodified loop")
-    ap.add_argument('--dump-gemm', default=None, help='write the per-launch GEMM profile of one step to this JSON file')
+    ap.add_argument('--dump-gemm', default=None, help='write the per-launch GEMM profile of one step to this JSON file (implies --full)')
     ap.add_argument('--config5', action='store_true',
                     help='BASELINE configs[4] instead of the training step: batch-256 fp16-storage inference in one hipGraph')
+    ap.add_argument('--full', action='store_true',
+                    help="also measure what is not the headline: the reference's eager loop, the live rooflines, the MANO "
+                         "micro-benchmark and the CPU baseline (each still switched off by its --no-* option); without it a run "
+                         "sets up, warms up, times the steps and prints the line")
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last one computed to DIR/<name>.npy (float32; larger tensors '
+                         'as a fixed seeded sample, 64 MB at most)')
     args = ap.parse_args()
+    if args.dump_gemm:
+        args.full = True            # the per-launch GEMM profile is taken by the roofline pass
+    if not args.full:
+        args.no_reference_loop = args.no_roofline = args.no_cpu_baseline = True
     if args.config5:
         claim_stdout()
         return config5(args)
@@ -509,6 +576,8 @@ def main():
         elapsed = float(t.item())
     final_loss = float(loss.item())
     comm_exposed = trainer.comm_ms_exposed() if trainer is not None else None
+    if args.dump_outputs and rank == 0:         # before the roofline pass, whose eager steps move the weights again
+        dump_outputs(args.dump_outputs, training_outputs(model, loss))
 
     roof = roof_hbm = roof_mano = None
     if not args.no_roofline and rank == 0:

@@ -41,11 +41,12 @@ def test_world_size_and_gpus_flag_must_agree():
 
 @pytest.mark.gpu
 def test_config5_line_carries_a_roofline():
-    """BASELINE configs[4] (`bench.py --config5`): the line names its workload, reports the deviation from the fp32 path and a
+    """BASELINE configs[4] (`bench.py --config5 --full`): the line names its workload, reports the deviation from the fp32 path and a
     `roofline` object with the matrix-pipe families of one forward (fp16-storage backbone, fp32 decoder, attention)."""
     env = dict(os.environ)
     env.pop('RIH_BENCH_SPAWN_PROBE', None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config5', '--batch', '16', '--steps', '2', '--warmup', '1'],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--config5', '--full', '--batch', '16', '--steps', '2',
+                        '--warmup', '1'],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])

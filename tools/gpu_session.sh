@@ -10,7 +10,7 @@ TAG=$1; shift
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 run() { name=$1; shift; echo "== $name: $*"; ( timeout "${T:-600}" "$@" ) > "$OUT/$name.log" 2>&1; echo "   exit $?"; tail -n 1 "$OUT/$name.log" | cut -c1-400; }
-QUICK="--no-cpu-baseline --no-reference-loop"
+QUICK="--full --no-cpu-baseline --no-reference-loop"
 for step in "$@"; do
   kind=${step%%:*}; arg=""; [ "$kind" != "$step" ] && arg=${step#*:}
   case $kind in
