@@ -543,7 +543,7 @@ int rih_mesh_loss_final(const float* partial_left, const float* partial_right, i
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 19
+#define RIH_ABI_VERSION 20
 #define RIH_ABI_NSIZES 12
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);
@@ -702,6 +702,33 @@ int rih_center_scale_bwd(const float* v, const float* j, const float* dvout, con
 int rih_hand_metrics(const float* v_pred, const float* v_gt, const float* j_pred, const float* j_gt, const float* Jreg,
                      int B, int V, int NJ, int root_idx, int bone_a, int bone_b, float* j_err_ori, float* v_err_ori,
                      float* j_err, float* v_err, float* pa, float* j_pred_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Hard mesh rasteriser and shader (csrc/rih_render.hip) -- the two-hand renderer of utils/vis_utils.py:39-289, which the
+ * reference builds on pytorch3d 0.7.2 (MeshRasterizer blur_radius 0 / faces_per_pixel 1, HardPhongShader, hard_rgb_blend);
+ * the semantics are written out in renderih_amd/render.py.  verts [B][V][3] world space, faces [F][3] int32 shared by the
+ * batch (indices in [0, V): checked by the caller), cams [B][16] = R (3x3 row-major, view = X R + T), T (3), focal (2),
+ * principal point (2) in NDC; cam_kind RIH_CAM_*.  Square images only: 1 <= H = W <= 4096; B <= 65535, B*F < 2^31.
+ *   rih_render_setup: face_rec [B][F][16] (may be NULL) = screen bounding box, screen vertices, view z, 1/(area + 1e-8), skip
+ *     flag; vnormals [B][V][3] (may be NULL, not both) = Meshes.verts_normals, gathered through the vertex -> (face, corner)
+ *     CSR vf_ptr [Vc+1] / vf_list (entries 3 f + corner, ascending per vertex; 1 <= Vc <= V, vertices >= Vc belong to no
+ *     face and get the normal 0).
+ *   rih_render_raster: pix_to_face [B][H][W] int32 = b F + f of the nearest covering face (ties: lower f) or -1; zbuf
+ *     [B][H][W] view z or -1; bary [B][H][W][3] (perspective-corrected under RIH_CAM_PERSPECTIVE) or -1.  Deterministic.
+ *   rih_render_shade: rgba [B][H][W][4] = hard_rgb_blend of the light_kind shading (RIH_LIGHT_POINT: PointLights at
+ *     (0, 0, -1), needs verts / vnormals / cams; RIH_LIGHT_AMBIENT: the texel) of colors [B][V][3] on a white background. */
+#define RIH_CAM_ORTHOGRAPHIC 0
+#define RIH_CAM_PERSPECTIVE 1
+#define RIH_LIGHT_POINT 0
+#define RIH_LIGHT_AMBIENT 1
+int rih_render_setup(const float* verts, const int32_t* faces, const int32_t* vf_ptr, const int32_t* vf_list,
+                     const float* cams, int cam_kind, int B, int V, int Vc, int F, float* face_rec, float* vnormals,
+                     void* stream);
+int rih_render_raster(const float* face_rec, int B, int F, int H, int W, int cam_kind, int32_t* pix_to_face, float* zbuf,
+                      float* bary, void* stream);
+int rih_render_shade(const int32_t* pix_to_face, const float* bary, const float* verts, const int32_t* faces,
+                     const float* vnormals, const float* colors, const float* cams, int light_kind, int B, int V, int F,
+                     int H, int W, float* rgba, void* stream);
 
 #ifdef __cplusplus
 }
