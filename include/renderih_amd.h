@@ -538,12 +538,35 @@ int rih_mesh_loss(const rih_mesh_topo* topo, const float* v3d_pred, const float*
 int rih_mesh_loss_final(const float* partial_left, const float* partial_right, int B, const float* term_weights,
                         const float* counts, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Fused MANO-head loss   (core/Loss_mano.py:62-219 ManoLoss, :245-335 mano_loss_GCN; csrc/rih_mano_loss.hip, ABI 21)
+ * Topology: the rih_mesh_topo of one hand as above; faces, vptr, vlist, J, V, F, NJ are read, perm / Vc / pool are not.
+ * rih_mano_loss (one launch per hand, one workgroup per image): predictions v3d_pred[B][V][3], v2d_pred[B][V][2],
+ *   pose_pred[B][pose_dim] (16 axis-angles, pose_dim must be 48), shape_pred[B][shape_dim] (shape_dim must be 10); labels
+ *   v3d_gt, v2d_gt, pose_gt, shape_gt; gt_shift[B][3] or NULL is added to v3d_gt (root_rel of the right hand).
+ *   term_weights[9] (DEVICE array, read at run time so that a captured hipGraph follows the epoch gate of the edge term;
+ *   order v2d, v3d, joint, normal, edge, pose, shape = LOSS_WEIGHT / element count / 2 (hand average), then MANO_REL / (3B),
+ *   then the regulariser's 0.005).  Writes the gradient of the total with respect to the four prediction tensors (the shape
+ *   gradient includes the regulariser's 0.01 * shape) and partial[B][8] (raw sums of the seven terms, then sum(shape^2)).
+ * rih_mano_loss_final (one workgroup): out[0] = total without the up-sampling term; out[1..9] = vert2d, vert3d, joint,
+ *   norm, edge, pose, shape (means, averaged over the hands), rootrel, regularize as the reference reports them;
+ *   counts[7] = element counts of the seven per-hand terms (DEVICE array); g_rootrel[B][3] = gradient of the total with
+ *   respect to rootrel_pred.  Partials are summed in a fixed order, no atomics: evaluations are bit-identical. */
+int rih_mano_loss(const rih_mesh_topo* topo, const float* v3d_pred, const float* v2d_pred, const float* pose_pred,
+                  const float* shape_pred, const float* v3d_gt, const float* v2d_gt, const float* pose_gt,
+                  const float* shape_gt, const float* gt_shift, int pose_dim, int shape_dim, const float* term_weights,
+                  float img_size, float* g_v3d, float* g_v2d, float* g_pose, float* g_shape, float* partial, int B,
+                  void* stream);
+int rih_mano_loss_final(const float* partial_left, const float* partial_right, const float* rootrel_pred,
+                        const float* rootrel_gt, int B, const float* term_weights, const float* counts, float* g_rootrel,
+                        float* out, void* stream);
+
 /* library / device info.  RIH_ABI_VERSION is bumped whenever a struct layout or a signature of this header changes;
  * rih_version() returns the value the library was compiled with and rih_abi_sizes() the sizeof of EVERY by-pointer struct, in
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 20
+#define RIH_ABI_VERSION 21
 #define RIH_ABI_NSIZES 12
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);

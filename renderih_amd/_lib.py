@@ -200,6 +200,9 @@ SIGNATURES = {
     'rih_mesh_loss': (c_i, [C.POINTER(MeshTopo), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_fl,
                             c_f, c_f, c_f, c_f, c_f, c_i, C.c_void_p]),
     'rih_mesh_loss_final': (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, C.c_void_p]),
+    'rih_mano_loss': (c_i, [C.POINTER(MeshTopo), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_fl,
+                            c_f, c_f, c_f, c_f, c_f, c_i, C.c_void_p]),
+    'rih_mano_loss_final': (c_i, [c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, C.c_void_p]),
     'rih_gemm_stats_rows': (c_i, [C.POINTER(GemmDesc)]),
     'rih_gemm_dropout_ok': (c_i, [C.POINTER(GemmDesc)]),
     'rih_gemm_engine': (c_i, [C.POINTER(GemmDesc)]),
@@ -220,7 +223,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 20     # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 21     # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 
