@@ -314,6 +314,19 @@ def _elem_profile(nbytes, tag, fn):
     return r
 
 
+def _profiled(flops, tag, fn):
+    """Run one MFMA-family launch; with ops.PROFILE set, bracket it with events on the launch stream and append
+    (flops, start, end, tag).  The only event bracket around such launches in the package.  tag: the 9-tuple bench.py parses, or a
+    thunk that returns it -- called behind the launch, and only when PROFILE is set (gemm's tag costs a library query)."""
+    if PROFILE is None:
+        return fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    PROFILE.append((flops, e0, e1, tag() if callable(tag) else tag))
+
+
 # BatchNorm training statistics from the convolution's GEMM epilogue (rih_gemm_desc.stats): `conv_bn` of the encoder installs
 # a holder around its convolution; the forward-type GEMM of that convolution fills it when its descriptor takes the split
 # engine's fast path (rih_gemm_stats_rows), and the BatchNorm behind it finishes the sums instead of reading the activation.
@@ -423,15 +436,9 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, a_mode=0, b_mode=0, bias=None, R=No
             d.stats = req.part.data_ptr()
     if collect is not None and collect.add(d, (A, B, Cout, amax_a, amax_b), 2.0 * M * N * K * nb1 * nb2):
         return
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(_L().rih_gemm(C.byref(d), _stream()), 'rih_gemm')
-        e1.record()
-        PROFILE.append((2.0 * M * N * K * nb1 * nb2, e0, e1, (M, N, K, nb1 * nb2, a_mode, b_mode, d.tile, splitk,
-                                                              int(_L().rih_gemm_engine(C.byref(d))))))
-        return fused_drop
-    check(_L().rih_gemm(C.byref(d), _stream()), 'rih_gemm')
+    _profiled(2.0 * M * N * K * nb1 * nb2,
+              lambda: (M, N, K, nb1 * nb2, a_mode, b_mode, d.tile, splitk, int(_L().rih_gemm_engine(C.byref(d)))),
+              lambda: check(_L().rih_gemm(C.byref(d), _stream()), 'rih_gemm'))
     return fused_drop
 
 
@@ -526,15 +533,9 @@ class GroupedGemms:
                 dev.copy_(host, non_blocking=True)
             else:
                 dev = host
-            if PROFILE is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                check(lib.rih_gemm_multi_launch(dev.data_ptr(), v, total.value, _stream()), 'rih_gemm_multi_launch')
-                e1.record()
-                PROFILE.append((sum(g[2] for g in group), e0, e1,
-                                (0, 0, 0, n, (v >> 2) & 1, (v >> 1) & 1, 20 + ((v & 63) >> 3), 0, 2 if v >= 64 else 1)))
-            else:
-                check(lib.rih_gemm_multi_launch(dev.data_ptr(), v, total.value, _stream()), 'rih_gemm_multi_launch')
+            _profiled(sum(g[2] for g in group),
+                      (0, 0, 0, n, (v >> 2) & 1, (v >> 1) & 1, 20 + ((v & 63) >> 3), 0, 2 if v >= 64 else 1),
+                      lambda: check(lib.rih_gemm_multi_launch(dev.data_ptr(), v, total.value, _stream()), 'rih_gemm_multi_launch'))
 
 
 # --------------------------------------------------------------------------------------------- weight gradients off the
@@ -718,6 +719,13 @@ def _wgrad_now(x, dy, dw, Kpix, Mrows, Ncols, ldx, ldy, geom, Cin_pad, taps, Cin
                                                   Ncols, _stream()), 'rih_splitk_reduce_bias_batched')
 
 
+def _relu_gate(dy, y):
+    """dy where y > 0, zero elsewhere (the backward of a ReLU epilogue), as a new tensor."""
+    dyr = torch.empty_like(dy)
+    check(_L().rih_relu_bwd(dy.data_ptr(), y.data_ptr(), dyr.data_ptr(), dy.numel(), _stream()), 'rih_relu_bwd')
+    return dyr
+
+
 def colsum(x2d, rows, Ccols, ldx=None):
     ldx = Ccols if ldx is None else ldx
     out = torch.empty((Ccols,), device=x2d.device, dtype=torch.float32)
@@ -849,6 +857,38 @@ def _halo3_ok(x, Cch, Nout, KH, KW, stride, pad, bias=None, residual=None):
             and x.is_contiguous() and x.data_ptr() % 16 == 0 and 4 * H * W_ * Cx < (1 << 31))
 
 
+def _e2_launch(entry, d, act, w, Cx, for_dgrad, Kp, bact, bw, stats, flops, tag, stats_rows=None):
+    """The launch sequence the engine-2 kernels of csrc/rih_conv3.hip share.  entry: 'rih_conv3x3' / 'rih_panel' / 'rih_rows' /
+    'rih_stem' -- the library's <entry>_ok, <entry>_stats_rows and <entry> are used.  d: the entry's descriptor, filled but for
+    w_h2, the two bounds and stats.  act: the activation operand; bact / bw: bounds (blocks or thunks) of it and of the OIHW weight
+    w, whose H2 operand is _h2_weight(w, Cx, for_dgrad) with a reduction of Kp.  stats: a StatsHolder to fill, or None; its block
+    height is `stats_rows` or the library's answer.  tag: the PROFILE 9-tuple, (output rows, output columns, ...).  Returns False,
+    with nothing enqueued and no bound resolved, when the library refuses the descriptor: the caller takes rih_gemm."""
+    lib = _L()
+    amax_act = 'amax_x' if hasattr(d, 'amax_x') else 'amax_a'         # (rih_conv3_desc / rih_panel_desc name it differently)
+    d.w_h2 = d.amax_w = act.data_ptr()          # (placeholders for the library's own precondition check)
+    setattr(d, amax_act, act.data_ptr())
+    if int(getattr(lib, entry + '_ok')(C.byref(d))) != 1:       # e.g. a view that is not 16-byte aligned
+        return False
+    # ONE bound block of w: the planes are scaled with it and the kernel un-scales with it (outside owned_bounds() every bound_of
+    # of a Parameter measures again, into a new block)
+    bwv = bw() if callable(bw) else bw
+    planes, kp = _h2_weight(w, Cx, for_dgrad, bound=bwv)
+    assert kp == Kp
+    d.w_h2 = planes.data_ptr()
+    setattr(d, amax_act, (bact() if callable(bact) else bact).data_ptr())
+    d.amax_w = bwv.data_ptr()
+    if stats is not None and stats.part is None:
+        M, N = tag[0], tag[1]
+        stats.rows = stats_rows if stats_rows is not None else int(getattr(lib, entry + '_stats_rows')(C.byref(d)))
+        assert stats.rows > 0
+        stats.T = M // stats.rows
+        stats.part = torch.empty((stats.T, 2, N), device=act.device, dtype=torch.float32)
+        d.stats = stats.part.data_ptr()
+    _profiled(flops, tag, lambda: check(getattr(lib, entry)(C.byref(d), _stream()), entry))
+    return True
+
+
 def conv3x3_halo(x, w, y, for_dgrad, relu=False, stats=None, bx=None, bw=None, R=None):
     """Enqueue rih_conv3x3: y = act(conv3x3(x, w)) (for_dgrad False; x [N,H,W,Cin], y [N,H,W,Cout]) or the data gradient
     y = conv3x3(x = dy, flipped w) (for_dgrad True; x [N,H,W,Cout], y [N,H,W,Cin]).  stats: a StatsHolder, filled.  bx / bw: bound
@@ -863,31 +903,8 @@ def conv3x3_halo(x, w, y, for_dgrad, relu=False, stats=None, bx=None, bw=None, R
         assert stats is None and tuple(R.shape) == tuple(y.shape)
         d.r, d.ldr = R.data_ptr(), Nout
     d.imgs, d.H, d.W, d.C, d.N, d.ldx, d.ldy, d.Kpad, d.relu = N, H, W_, Cch, Nout, Cch, Nout, 9 * Cch, 1 if relu else 0
-    d.w_h2 = d.amax_x = d.amax_w = x.data_ptr()         # (placeholders for the library's own precondition check)
-    if int(_L().rih_conv3x3_ok(C.byref(d))) != 1:       # e.g. an output view that is not 16-byte aligned: the caller takes rih_gemm
-        return False
-    bwv = bw() if callable(bw) else bw      # ONE bound block of w: the planes are scaled with it and the kernel un-scales with it
-    planes, Kp = _h2_weight(w, (Cch if not for_dgrad else Nout), for_dgrad, bound=bwv)
-    assert Kp == 9 * Cch
-    d.w_h2 = planes.data_ptr()
-    d.amax_x = (bx() if callable(bx) else bx).data_ptr()
-    d.amax_w = bwv.data_ptr()
-    if stats is not None and stats.part is None:
-        stats.rows = int(_L().rih_conv3x3_stats_rows(C.byref(d)))
-        assert stats.rows > 0
-        stats.T = (N * H * W_) // stats.rows
-        stats.part = torch.empty((stats.T, 2, Nout), device=x.device, dtype=torch.float32)
-        d.stats = stats.part.data_ptr()
-    flops = 2.0 * N * H * W_ * Nout * 9 * Cch
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(_L().rih_conv3x3(C.byref(d), _stream()), 'rih_conv3x3')
-        e1.record()
-        PROFILE.append((flops, e0, e1, (N * H * W_, Nout, 9 * Cch, 1, 0, 3, 50, 1, 2)))
-        return True
-    check(_L().rih_conv3x3(C.byref(d), _stream()), 'rih_conv3x3')
-    return True
+    return _e2_launch('rih_conv3x3', d, x, w, (Cch if not for_dgrad else Nout), for_dgrad, 9 * Cch, bx, bw, stats,
+                      2.0 * N * H * W_ * Nout * 9 * Cch, (N * H * W_, Nout, 9 * Cch, 1, 0, 3, 50, 1, 2))
 
 
 # --------------------------------------------------------------------------------------------- short-K streaming GEMM
@@ -909,45 +926,31 @@ def _panel_ok(a2d_rows, K, N, lda, a, bias=None):
     return (a2d_rows // (8192 // K)) * (N // bn) >= 256
 
 
-def panel_gemm(a, w, c, M, N, K, lda, ldc, for_dgrad, relu=False, stats=None, R=None, ldr=0, ba=None, bw=None):
-    """Enqueue rih_panel: c[M][N] = act(a[M][K] W^T (+ R)) with W = the OIHW 1x1 weight `w` as forward (n = co, k = ci) or
-    data-gradient (n = ci, k = co) H2 operand.  stats: a StatsHolder, filled.  ba / bw: bound thunks of a and w.  Returns False
-    (nothing enqueued) when the library refuses the descriptor (rih_panel_ok)."""
+def _plain_rows_launch(entry, code, a, w, c, M, N, K, lda, ldc, for_dgrad, relu, stats, R, ldr, ba, bw):
+    """panel_gemm / rows_gemm: one descriptor (rih_panel_desc), one contract; `code` is the kernel's number in the PROFILE tag.
+    The statistics epilogue is not taken together with a residual."""
     from ._lib import PanelDesc
     Cout, Cin = w.shape[0], w.shape[1]
     d = PanelDesc()
     d.a, d.c, d.r = a.data_ptr(), c.data_ptr(), _p(R)
     d.M, d.N, d.K, d.lda, d.ldc, d.ldr, d.relu = M, N, K, lda, ldc, ldr, 1 if relu else 0
-    d.w_h2 = d.amax_a = d.amax_w = a.data_ptr()         # (placeholders for the library's own precondition check)
-    if int(_L().rih_panel_ok(C.byref(d))) != 1:         # e.g. a dskip view that is not 16-byte aligned: the caller takes rih_gemm
-        return False
-    bwv = bw() if callable(bw) else bw
-    planes, Kp = _h2_weight(w, Cin, for_dgrad, bound=bwv)
-    assert Kp == K and (N, K) == ((Cin, Cout) if for_dgrad else (Cout, Cin))
-    d.w_h2 = planes.data_ptr()
-    d.amax_a = (ba() if callable(ba) else ba).data_ptr()
-    d.amax_w = bwv.data_ptr()
-    if stats is not None and stats.part is None and R is None:
-        stats.rows = int(_L().rih_panel_stats_rows(C.byref(d)))
-        assert stats.rows > 0
-        stats.T = M // stats.rows
-        stats.part = torch.empty((stats.T, 2, N), device=a.device, dtype=torch.float32)
-        d.stats = stats.part.data_ptr()
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(_L().rih_panel(C.byref(d), _stream()), 'rih_panel')
-        e1.record()
-        PROFILE.append((2.0 * M * N * K, e0, e1, (M, N, K, 1, 0, 3, 51, 1, 2)))
-        return True
-    check(_L().rih_panel(C.byref(d), _stream()), 'rih_panel')
-    return True
+    assert (N, K) == ((Cin, Cout) if for_dgrad else (Cout, Cin))
+    return _e2_launch(entry, d, a, w, Cin, for_dgrad, K, ba, bw, stats if R is None else None,
+                      2.0 * M * N * K, (M, N, K, 1, 0, 3, code, 1, 2))
+
+
+def panel_gemm(a, w, c, M, N, K, lda, ldc, for_dgrad, relu=False, stats=None, R=None, ldr=0, ba=None, bw=None):
+    """Enqueue rih_panel: c[M][N] = act(a[M][K] W^T (+ R)) with W = the OIHW 1x1 weight `w` as forward (n = co, k = ci) or
+    data-gradient (n = ci, k = co) H2 operand.  stats: a StatsHolder, filled.  ba / bw: bound thunks of a and w.  Returns False
+    (nothing enqueued) when the library refuses the descriptor (rih_panel_ok)."""
+    return _plain_rows_launch('rih_panel', 51, a, w, c, M, N, K, lda, ldc, for_dgrad, relu, stats, R, ldr, ba, bw)
 
 
 # --------------------------------------------------------------------------------------------- long-K plain-row GEMM
 # csrc/rih_conv3.hip rows_kernel (round 6): the 1x1 convolutions with K >= ROWS_MINK on plain rows (Bottleneck.conv1 / conv3 of layer1-4
-# forward, their data gradients) as 512-thread workgroups on up to 256 x 128 tiles with the H2 weight planes staged by LDS-DMA and three
-# A stages.  RIH_ROWS=0: rih_gemm's tiled kernels.  RIH_ROWS_MINK: smallest reduction that goes there (shorter ones: rih_panel / tiled).
+# forward, their data gradients) as 512-thread workgroups on up to 256 x 128 tiles with three stages of H2 weight planes staged by
+# LDS-DMA, two A stages in LDS and the A prefetch in registers.  RIH_ROWS=0: rih_gemm's tiled kernels.  RIH_ROWS_MINK: smallest
+# reduction that goes there (shorter ones: rih_panel / tiled).
 ROWS = os.environ.get('RIH_ROWS', '1') == '1'
 ROWS_MINK = int(os.environ.get('RIH_ROWS_MINK', '256'))
 ROWS_MIN_WGS = int(os.environ.get('RIH_ROWS_MIN_WGS', '128'))
@@ -979,35 +982,7 @@ def rows_gemm(a, w, c, M, N, K, lda, ldc, for_dgrad, relu=False, stats=None, R=N
     """Enqueue rih_rows: c[M][N] = act(a[M][K] W^T (+ R)) with W = the OIHW 1x1 weight `w` as forward (n = co, k = ci) or
     data-gradient (n = ci, k = co) H2 operand.  stats: a StatsHolder, filled.  ba / bw: bound thunks of a and w.  Returns False
     (nothing enqueued) when the library refuses the descriptor: the caller then takes rih_gemm."""
-    from ._lib import PanelDesc
-    Cout, Cin = w.shape[0], w.shape[1]
-    d = PanelDesc()
-    d.a, d.c, d.r = a.data_ptr(), c.data_ptr(), _p(R)
-    d.M, d.N, d.K, d.lda, d.ldc, d.ldr, d.relu = M, N, K, lda, ldc, ldr, 1 if relu else 0
-    d.w_h2 = d.amax_a = d.amax_w = a.data_ptr()         # (placeholders for the library's own precondition check)
-    if int(_L().rih_rows_ok(C.byref(d))) != 1:
-        return False
-    bwv = bw() if callable(bw) else bw                  # ONE bound block of w: the planes are scaled with it and the kernel unscales with it
-    planes, Kp = _h2_weight(w, Cin, for_dgrad, bound=bwv)
-    assert Kp == K and (N, K) == ((Cin, Cout) if for_dgrad else (Cout, Cin))
-    d.w_h2 = planes.data_ptr()
-    d.amax_a = (ba() if callable(ba) else ba).data_ptr()
-    d.amax_w = bwv.data_ptr()
-    if stats is not None and stats.part is None and R is None:
-        stats.rows = int(_L().rih_rows_stats_rows(C.byref(d)))
-        assert stats.rows > 0
-        stats.T = M // stats.rows
-        stats.part = torch.empty((stats.T, 2, N), device=a.device, dtype=torch.float32)
-        d.stats = stats.part.data_ptr()
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(_L().rih_rows(C.byref(d), _stream()), 'rih_rows')
-        e1.record()
-        PROFILE.append((2.0 * M * N * K, e0, e1, (M, N, K, 1, 0, 3, 52, 1, 2)))
-        return True
-    check(_L().rih_rows(C.byref(d), _stream()), 'rih_rows')
-    return True
+    return _plain_rows_launch('rih_rows', 52, a, w, c, M, N, K, lda, ldc, for_dgrad, relu, stats, R, ldr, ba, bw)
 
 
 # --------------------------------------------------------------------------------------------- stem convolution
@@ -1026,29 +1001,35 @@ def stem_conv(x, w, y, relu=False, stats=None, bx=None, bw=None):
     d = Conv3Desc()
     d.x, d.y = x.data_ptr(), y.data_ptr()
     d.imgs, d.H, d.W, d.C, d.N, d.ldx, d.ldy, d.Kpad, d.relu = N, H, W_, Cx, Cout, Cx, Cout, 224, 1 if relu else 0
-    d.w_h2 = d.amax_x = d.amax_w = x.data_ptr()         # (placeholders for the library's own precondition check)
-    if int(_L().rih_stem_ok(C.byref(d))) != 1:
-        return False
-    bwv = bw() if callable(bw) else bw
-    planes, Kp = _h2_weight(w, Cx, False, bound=bwv)
-    assert Kp == 224
-    d.w_h2 = planes.data_ptr()
-    d.amax_x = (bx() if callable(bx) else bx).data_ptr()
-    d.amax_w = bwv.data_ptr()
     M = N * (H // 2) * (W_ // 2)
-    if stats is not None and stats.part is None:
-        stats.rows, stats.T = 64, M // 64
-        stats.part = torch.empty((stats.T, 2, Cout), device=x.device, dtype=torch.float32)
-        d.stats = stats.part.data_ptr()
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        check(_L().rih_stem(C.byref(d), _stream()), 'rih_stem')
-        e1.record()
-        PROFILE.append((2.0 * M * Cout * 49 * Cx, e0, e1, (M, Cout, 49 * Cx, 1, 0, 3, 53, 1, 2)))
+    # the statistics blocks are 64 rows high, always: the library has no rih_stem_stats_rows
+    return _e2_launch('rih_stem', d, x, w, Cx, False, 224, bx, bw, stats,
+                      2.0 * M * Cout * 49 * Cx, (M, Cout, 49 * Cx, 1, 0, 3, 53, 1, 2), stats_rows=64)
+
+
+def _e2_conv(a, w, y, for_dgrad, stride, pad, bias=None, relu=False, stats=None, R=None, ba=None, bw=None):
+    """The engine-2 kernels a convolution tries before rih_gemm, in this order: halo-resident 3x3, stem (forward only), panel, rows.
+    Forward (for_dgrad False): a = x [N,H,W,Cx], y [N,Ho,Wo,Cout]; stride-1 data gradient (for_dgrad True): a = dy [N,Ho,Wo,Cout],
+    y = dx [N,H,W,Cx], R = the skip path's gradient.  ba / bw: bound thunks of a and of the OIHW weight w.  True: one of them took
+    the launch; False: nothing enqueued.  Rules and launchers are looked up in the module at every call, like the switches."""
+    Cout, Cin, KH, KW = w.shape
+    Cx = (y if for_dgrad else a).shape[-1]          # channels of the convolution's input map (>= Cin: padded channels)
+    M, K = a.numel() // a.shape[-1], a.shape[-1]
+    Nn = y.shape[-1]
+    if (Cx == Cin and _halo3_ok(a, K, Nn, KH, KW, stride, pad, bias, R)
+            and conv3x3_halo(a, w, y, for_dgrad, relu=relu, stats=stats, bx=ba, bw=bw, R=R)):
         return True
-    check(_L().rih_stem(C.byref(d), _stream()), 'rih_stem')
-    return True
+    if (not for_dgrad and STEM and ENGINE == 2 and KH == 7 and KW == 7 and stride == 2 and pad == 3 and Cx == 4 and Cout == 64
+            and bias is None and a.is_contiguous() and stem_conv(a, w, y, relu=relu, stats=stats, bx=ba, bw=bw)):
+        return True
+    if not (KH * KW == 1 and Cx == Cin and stride == 1 and pad == 0):       # below: plain-row GEMMs on the stored [Cout][Cin] weight
+        return False
+    ldr = Nn if for_dgrad else 0
+    if (_panel_ok(M, K, Nn, K, a, bias)
+            and panel_gemm(a, w, y, M, Nn, K, K, Nn, for_dgrad, relu=relu, stats=stats, R=R, ldr=ldr, ba=ba, bw=bw)):
+        return True
+    return bool(_rows_ok(M, K, Nn, K, a, bias)
+                and rows_gemm(a, w, y, M, Nn, K, K, Nn, for_dgrad, relu=relu, stats=stats, R=R, ldr=ldr, ba=ba, bw=bw))
 
 
 class Conv2dFn(torch.autograd.Function):
@@ -1072,18 +1053,7 @@ class Conv2dFn(torch.autograd.Function):
         geom = (H, W_, Cx, Ho, Wo, KH, KW, stride, 1, pad, pad)
         # engine 2: operand bounds (kept for the backward: x is the weight gradient's A operand, w the data gradient's B)
         bx, bw = (LazyBound(x), LazyBound(w)) if ENGINE == 2 else (None, None)
-        rows1x1 = KH * KW == 1 and Cx == Cin and stride == 1 and pad == 0       # a plain-row GEMM on the stored [Cout][Cin] weight
-        if (Cx == Cin and _halo3_ok(x, Cx, Cout, KH, KW, stride, pad, bias)
-                and conv3x3_halo(x, w, y, False, relu=relu, stats=stats, bx=bx, bw=bw)):
-            pass
-        elif (STEM and ENGINE == 2 and KH == 7 and KW == 7 and stride == 2 and pad == 3 and Cx == 4 and Cout == 64 and bias is None
-              and x.is_contiguous() and stem_conv(x, w, y, relu=relu, stats=stats, bx=bx, bw=bw)):
-            pass
-        elif (rows1x1 and _panel_ok(M, Cin, Cout, Cx, x, bias)
-              and panel_gemm(x, w, y, M, Cout, Cin, Cx, Cout, False, relu=relu, stats=stats, ba=bx, bw=bw)):
-            pass
-        elif (rows1x1 and _rows_ok(M, Cin, Cout, Cx, x, bias)
-              and rows_gemm(x, w, y, M, Cout, Cin, Cx, Cout, False, relu=relu, stats=stats, ba=bx, bw=bw)):
+        if _e2_conv(x, w, y, False, stride, pad, bias=bias, relu=relu, stats=stats, ba=bx, bw=bw):
             pass
         elif KH * KW == 1 and Cx == Cin:
             gemm(x, w, y, M, Cout, K, Cx, Cin, Cout, a_mode=0, b_mode=1, bias=bias, relu=relu, geom=geom, stats=stats,
@@ -1112,13 +1082,10 @@ class Conv2dFn(torch.autograd.Function):
         dy = _c(dy)
         _, Ho, Wo, _ = dy.shape
         M = N * Ho * Wo
-        lib = _L()
         bx, bw = ctx.bounds
         bdy = LazyBound(dy) if bx is not None else None     # (also bounds the ReLU-gated gradient below)
         if relu:
-            dyr = torch.empty_like(dy)
-            check(lib.rih_relu_bwd(dy.data_ptr(), y.data_ptr(), dyr.data_ptr(), dy.numel(), _stream()), 'rih_relu_bwd')
-            dy = dyr
+            dy = _relu_gate(dy, y)
         dx = dw = db = None
         if ctx.needs_input_grad[0] and stride > 1:
             # strided conv: s*s dense sub-convolutions, one per parity class (oh, ow) of the input pixel; class rows
@@ -1151,15 +1118,7 @@ class Conv2dFn(torch.autograd.Function):
             dx = torch.empty_like(x)
             Mx = N * H * W_
             geom = (Ho, Wo, Cout, H, W_, KH, KW, 1, stride, KH - 1 - pad, KW - 1 - pad)
-            rows1x1 = KH * KW == 1 and Cx == Cin and stride == 1 and pad == 0
-            if (Cx == Cin and _halo3_ok(dy, Cout, Cx, KH, KW, stride, pad, None, dskip)
-                    and conv3x3_halo(dy, w, dx, True, bx=bdy, bw=bw, R=dskip)):
-                pass
-            elif (rows1x1 and _panel_ok(Mx, Cout, Cin, Cout, dy)
-                  and panel_gemm(dy, w, dx, Mx, Cin, Cout, Cout, Cx, True, R=dskip, ldr=Cx, ba=bdy, bw=bw)):
-                pass
-            elif (rows1x1 and _rows_ok(Mx, Cout, Cin, Cout, dy)
-                  and rows_gemm(dy, w, dx, Mx, Cin, Cout, Cout, Cx, True, R=dskip, ldr=Cx, ba=bdy, bw=bw)):
+            if _e2_conv(dy, w, dx, True, stride, pad, R=dskip, ba=bdy, bw=bw):
                 pass
             elif KH * KW == 1 and Cx == Cin:
                 gemm(dy, w, dx, Mx, Cin, Cout, Cout, Cin, Cx, a_mode=0, b_mode=0, geom=geom, R=dskip, ldr=Cx,
@@ -1240,9 +1199,7 @@ class ConvCat1x1Fn(torch.autograd.Function):
         M = N * H * W_
         Cin = w.shape[1]
         if relu_bwd:
-            dyr = torch.empty_like(dy)
-            check(_L().rih_relu_bwd(dy.data_ptr(), y.data_ptr(), dyr.data_ptr(), dy.numel(), _stream()), 'rih_relu_bwd')
-            dy = dyr
+            dy = _relu_gate(dy, y)
         bdy = LazyBound(dy) if bw is not None else None
         wflat = w.view(Cout, Cin)
         dparts = []
@@ -1389,14 +1346,13 @@ class LinearFn(torch.autograd.Function):
         if residual is not None:
             residual = _c(residual)
         bx, bw = _lin_bounds(x, w)
-        if drop is not None and drop[0] > 0:
-            assert not (relu and residual is not None)
-            fused = gemm(x, w, y, M, Nf, K, K, K, Nf, a_mode=0, b_mode=1, bias=bias, R=residual, ldr=Nf, relu=relu, drop=drop,
-                         amax_a=bx, amax_b=bw)
-            y = _finish_dropout(fused, y, residual, drop)
-        else:
+        if drop is not None and not drop[0] > 0:
             drop = None
-            gemm(x, w, y, M, Nf, K, K, K, Nf, a_mode=0, b_mode=1, bias=bias, R=residual, ldr=Nf, relu=relu, amax_a=bx, amax_b=bw)
+        assert drop is None or not (relu and residual is not None)
+        fused = gemm(x, w, y, M, Nf, K, K, K, Nf, a_mode=0, b_mode=1, bias=bias, R=residual, ldr=Nf, relu=relu, drop=drop,
+                     amax_a=bx, amax_b=bw)
+        if drop is not None:
+            y = _finish_dropout(fused, y, residual, drop)
         ctx.save_for_backward(x, w, y if relu else None)
         ctx.cfg = (relu, bias is not None, residual is not None, drop)
         ctx.bounds = (bx, bw)
@@ -1409,14 +1365,11 @@ class LinearFn(torch.autograd.Function):
         Nf, K = w.shape
         M = x.numel() // K
         dy = _c(dy)
-        lib = _L()
         dres = dy if (has_res and ctx.needs_input_grad[3]) else None     # (with drop: the residual joins behind the dropout)
         if drop is not None:
             dy = _dropout_grad(dy, drop)
         if relu:
-            dyr = torch.empty_like(dy)
-            check(lib.rih_relu_bwd(dy.data_ptr(), y.data_ptr(), dyr.data_ptr(), dy.numel(), _stream()), 'rih_relu_bwd')
-            dy = dyr
+            dy = _relu_gate(dy, y)
         dx = dw = db = None
         bx, bw = ctx.bounds
         bdy = LazyBound(dy) if bx is not None else None
@@ -1471,15 +1424,13 @@ class LinearPairFn(torch.autograd.Function):
         if residual is not None:
             residual = _c(residual)
         bx, bw = _lin_bounds(x, wL, None if stacked else wR)
-        if drop is not None and drop[0] > 0:
-            assert not (relu and residual is not None)
-            fused = gemm(x, wL, y, M, Nf, K, K, K, Nf, a_mode=0, b_mode=1, bias=bL, R=residual, ldr=Nf, relu=relu, nb1=2,
-                         sA=(M * K, 0), sB=(sW, 0), sC=(M * Nf, 0), sBias=sBias, sR=M * Nf, drop=drop, amax_a=bx, amax_b=bw)
-            y = _finish_dropout(fused, y, residual, drop)
-        else:
+        if drop is not None and not drop[0] > 0:
             drop = None
-            gemm(x, wL, y, M, Nf, K, K, K, Nf, a_mode=0, b_mode=1, bias=bL, R=residual, ldr=Nf, relu=relu, nb1=2,
-                 sA=(M * K, 0), sB=(sW, 0), sC=(M * Nf, 0), sBias=sBias, sR=M * Nf, amax_a=bx, amax_b=bw)
+        assert drop is None or not (relu and residual is not None)
+        fused = gemm(x, wL, y, M, Nf, K, K, K, Nf, a_mode=0, b_mode=1, bias=bL, R=residual, ldr=Nf, relu=relu, nb1=2,
+                     sA=(M * K, 0), sB=(sW, 0), sC=(M * Nf, 0), sBias=sBias, sR=M * Nf, drop=drop, amax_a=bx, amax_b=bw)
+        if drop is not None:
+            y = _finish_dropout(fused, y, residual, drop)
         ctx.save_for_backward(x, wL, wR, y if relu else None)
         ctx.cfg = (relu, bL is not None, residual is not None, stacked, Nf, K, sW, drop)
         ctx.bounds = (bx, bw)
@@ -1495,9 +1446,7 @@ class LinearPairFn(torch.autograd.Function):
         if drop is not None:
             dy = _dropout_grad(dy, drop)
         if relu:
-            dyr = torch.empty_like(dy)
-            check(_L().rih_relu_bwd(dy.data_ptr(), y.data_ptr(), dyr.data_ptr(), dy.numel(), _stream()), 'rih_relu_bwd')
-            dy = dyr
+            dy = _relu_gate(dy, y)
         dx = None
         bx, bw = ctx.bounds
         bdy = LazyBound(dy) if bx is not None else None
@@ -1570,9 +1519,7 @@ class PatchConvPairFn(torch.autograd.Function):
         N, H, W_, Cx = x.shape
         g_h, g_w = H // KH, W_ // KW
         M, K = N * g_h * g_w, KH * KW * Cx
-        dy = _c(dy)
-        dyr = torch.empty_like(dy)
-        check(_L().rih_relu_bwd(dy.data_ptr(), y.data_ptr(), dyr.data_ptr(), dy.numel(), _stream()), 'rih_relu_bwd')
+        dyr = _relu_gate(_c(dy), y)
         dx = None
         if ctx.needs_input_grad[0]:
             dxp = torch.empty((2, M, K), device=x.device, dtype=torch.float32)       # rows = patches, cols = (kh, kw, ci)
@@ -1990,17 +1937,6 @@ FLASH_ATTN = os.environ.get('RIH_FLASH_ATTN', '1') == '1'
 
 def _flash_ok(d, B, heads):
     return FLASH_ATTN and not FUSED_ATTN and d in (16, 32, 64) and B * heads <= 65535
-
-
-def _profiled(flops, tag, fn):
-    """Run one MFMA-family launch; with ops.PROFILE set, bracket it with events like rih_gemm launches."""
-    if PROFILE is None:
-        return fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    PROFILE.append((flops, e0, e1, tag))
 
 
 def _attn_forward(q, q_ld, k, v, kv_ld, B, Sq, Sk, D, heads, drop_p, seed, device, out=None):

@@ -332,7 +332,7 @@ ROWS_CASES = [(2, 16, 16, 256, 64, False, True), (1, 16, 8, 96, 128, True, True)
 @pytest.mark.parametrize('case', ROWS_CASES)
 def test_rows_1x1(case, monkeypatch=None):
     """csrc/rih_conv3.hip rows_kernel through ops.conv2d / ops.conv2d_skip (ops.ROWS, engine 2): 1x1 convolutions with a long reduction
-    as 512-thread workgroups with LDS-DMA-staged H2 weight planes and three A stages -- forward (+ ReLU, + BatchNorm statistics), the
+    as 512-thread workgroups with three LDS-DMA-staged stages of H2 weight planes, two A stages in LDS and the A prefetch in registers -- forward (+ ReLU, + BatchNorm statistics), the
     data gradient WITH the skip path's gradient as residual (conv2d_skip: Bottleneck.conv1), the weight gradient (rih_gemm) --
     against fp64 (gradients at rtol 1e-4 + 1e-5 max: north_star's bar), and against the tiled kernels (ROWS off).  The planning
     thresholds (K >= 256, N >= 128, >= 128 workgroups) are lifted for the small shapes; the panel kernel is off so that K = 64 / 128 come here."""
