@@ -566,7 +566,7 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 21
+#define RIH_ABI_VERSION 22
 #define RIH_ABI_NSIZES 12
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);
@@ -688,6 +688,34 @@ int rih_prepare_labels(const float* p2, const float* p3, int B, int NV, int NJ, 
  * -1 + (i + 0.5) * 2/(G-1) to the closest triangle when the centre is inside the mesh (odd crossing count towards the
  * corner (-1,-1,-1)), else 0.  No gradient (as in the reference). */
 int rih_sdf(float* phi, const int32_t* faces, const float* vertices, int B, int F, int V, int G, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Fused two-hand penetration loss of the pose optimiser (pose_data_optimize/code_sdf/sdf_template.py:19-157 `NewLoss`;
+ * csrc/rih_sdf_loss.hip + the sparse voxeliser of csrc/rih_sdf.hip; renderih_amd.sdf.FusedTwoHandSDFLoss, ABI 22).
+ * vertices [bs][2][V][3], hand 0 = right, 1 = left; "mesh" m = 2 b + h, N = 2 bs meshes, 2 <= G <= 256.
+ * rih_two_hand_prep (one workgroup per mesh): box[m] = {centre xyz = (lo + hi) / 2, scale = scale_mul * max axis of
+ *   (hi - lo)}; vnorm[m][V][3] = (v - centre) / scale, the voxeliser's input; flags[m][G^3] (bytes) = 1 at every voxel that
+ *   a vertex of the OTHER hand of the sample reads when it samples mesh m's field (its trilinear corners inside the grid,
+ *   sample index ((p + 1) / 2) (G - 1), align_corners = True), else 0; list[m][max_count] = the flagged voxels in ascending
+ *   order, count[m] of them.  max_count = min(G^3, 8 V) is the stride of `list`.
+ * rih_sdf_sparse: rih_sdf at the voxels list[b][0 .. count[b]) only (same per-voxel device function, bit-identical values);
+ *   the other voxels of phi are not written.  The grid covers max_count voxels per mesh; workgroups beyond count[b] exit.
+ * rih_two_hand_sample (one workgroup per sample): s = trilinear sample (zero padding) of phi[other hand's mesh] at every
+ *   vertex; per_vert[b][2][V] = weight[v] s / 4 (index 0 = LEFT vertices in the right hand's field, 1 = right: the order of
+ *   the reference's loss_per_vert); ori[b][2][V] = weight[v] s scale(sampled cube); grad[b][2][V][3] = weight[v] ds/dvertex
+ *   (grid_sample's backward x (G - 1) / 2 / scale; corners outside the grid contribute 0); loss[b] = sum of per_vert[b] in a
+ *   fixed order.  weight[V] int32 = how many of the 16 hand parts hold the vertex.
+ * rih_two_hand_bwd (elementwise): g_vertices[b][h][v][:] = grad[b][1 - h][v][:] * (g_loss[b] / 4 + g_pv[b][1 - h][v] / 4 +
+ *   g_ori[b][1 - h][v] * scale(sampled cube)); each of g_loss, g_pv, g_ori may be NULL (that output was not used).
+ * No float atomics, fixed summation order: evaluations are bit-identical. */
+int rih_two_hand_prep(const float* vertices, float scale_mul, float* box, float* vnorm, uint8_t* flags, int32_t* list,
+                      int32_t* count, int bs, int V, int G, int max_count, void* stream);
+int rih_sdf_sparse(float* phi, const int32_t* faces, const float* vertices, const int32_t* list, const int32_t* count,
+                   int max_count, int B, int F, int V, int G, void* stream);
+int rih_two_hand_sample(const float* phi, const float* vertices, const float* box, const int32_t* weight, float* per_vert,
+                        float* ori, float* grad, float* loss, int bs, int V, int G, void* stream);
+int rih_two_hand_bwd(const float* grad, const float* box, const float* g_loss, const float* g_pv, const float* g_ori,
+                     float* g_vertices, int bs, int V, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * MANO parameter head of the reference's `load_new_model` network (common/myhand/decoder_lijun_mano.py:112-160,247-300)

@@ -98,6 +98,10 @@ SIGNATURES = {
     'rih_attention_bwd_dkv_fused': (c_i, [c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_f, c_f, c_i,
                                           C.c_void_p]),
     'rih_sdf': (c_i, [c_f, C.c_void_p, c_f, c_i, c_i, c_i, c_i, C.c_void_p]),
+    'rih_two_hand_prep': (c_i, [c_f, c_fl, c_f, c_f, C.c_void_p, C.c_void_p, C.c_void_p, c_i, c_i, c_i, c_i, C.c_void_p]),
+    'rih_sdf_sparse': (c_i, [c_f, C.c_void_p, c_f, C.c_void_p, C.c_void_p, c_i, c_i, c_i, c_i, c_i, C.c_void_p]),
+    'rih_two_hand_sample': (c_i, [c_f, c_f, c_f, C.c_void_p, c_f, c_f, c_f, c_f, c_i, c_i, c_i, C.c_void_p]),
+    'rih_two_hand_bwd': (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, C.c_void_p]),
     'rih_render_setup': (c_i, [c_f, C.c_void_p, C.c_void_p, C.c_void_p, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f,
                                 C.c_void_p]),
     'rih_render_raster': (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, C.c_void_p, c_f, c_f, C.c_void_p]),
@@ -223,7 +227,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 21     # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 22     # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 

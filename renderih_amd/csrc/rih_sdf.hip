@@ -9,7 +9,8 @@
 // faces (gathered cooperatively, one face per lane) and every lane then reads them as LDS broadcasts: F x 36 bytes per
 // workgroup from L2 instead of per thread.  The per-face arithmetic follows the reference's order of operations so that the
 // CPU restatement (oracle/sdf_oracle.py) agrees to rounding.  Compute-bound on fp32 VALU (~150 flops per voxel-face pair).
-// STATUS: harness-verified against the oracle; not yet run on a GPU.
+// rih_sdf_sparse evaluates a listed subset of the voxels with the same per-voxel device function (voxel_faces) for the
+// two-hand penetration loss (csrc/rih_sdf_loss.hip), which reads at most 8 voxels per sampled vertex.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/renderih_amd.h"
@@ -82,6 +83,42 @@ __device__ __forceinline__ bool ray_triangle(const float* orig, const float* dir
     return true;
 }
 
+// Voxel `tid` of the G^3 grid: its centre c and the parity ray's direction (towards the corner (-1,-1,-1)).
+__device__ __forceinline__ void voxel_centre(int tid, int G, float* c, float* dir) {
+    const int i = tid % G, j = (tid / G) % G, k = tid / (G * G);
+    const float dx = 2.f / (float)(G - 1);
+    c[0] = -1.f + ((float)i + 0.5f) * dx; c[1] = -1.f + ((float)j + 0.5f) * dx; c[2] = -1.f + ((float)k + 0.5f) * dx;
+    dir[0] = -1.f - c[0]; dir[1] = -1.f - c[1]; dir[2] = -1.f - c[2];
+}
+
+// Faces f0 .. f0 + FT of mesh vb into LDS, one face per lane of the first FT threads (callers put a barrier on each side).
+__device__ __forceinline__ void stage_faces(float (*tri)[9], const int32_t* __restrict__ faces, const float* __restrict__ vb,
+                                            int f0, int F) {
+    if (threadIdx.x < FT && f0 + (int)threadIdx.x < F) {
+        const int32_t* fc = faces + 3 * (f0 + threadIdx.x);
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            const float* vp = vb + 3 * fc[p];
+            tri[threadIdx.x][3 * p] = vp[0];
+            tri[threadIdx.x][3 * p + 1] = vp[1];
+            tri[threadIdx.x][3 * p + 2] = vp[2];
+        }
+    }
+}
+
+// The per-voxel arithmetic of BOTH voxelisers: faces fbeg, fbeg + fstep, ... < n of the staged tile against one voxel.  The
+// nearest distance is a minimum and the crossing count a sum of integers, so any split of the faces gives the same bits.
+__device__ __forceinline__ void voxel_faces(float (*tri)[9], int n, int fbeg, int fstep, const float* c,
+                                            const float* dir, float& best, int& hits) {
+    for (int f = fbeg; f < n; f += fstep) {
+        const float* t = tri[f];
+        float r[3], tt;
+        point_triangle(c, t, t + 3, t + 6, r);
+        best = fminf(best, dist3(c, r));
+        if (ray_triangle(c, dir, t, t + 3, t + 6, &tt) && tt >= 0.f) ++hits;
+    }
+}
+
 __global__ __launch_bounds__(TPB) void sdf_kernel(float* __restrict__ phi, const int32_t* __restrict__ faces,
                                                   const float* __restrict__ vertices, int F, int V, int G) {
     __shared__ float tri[FT][9];
@@ -89,37 +126,58 @@ __global__ __launch_bounds__(TPB) void sdf_kernel(float* __restrict__ phi, const
     const int b = blockIdx.y;
     const int tid = blockIdx.x * TPB + threadIdx.x;
     const bool live = tid < vox;
-    const int i = tid % G, j = (tid / G) % G, k = tid / (G * G);
-    const float dx = 2.f / (float)(G - 1);
-    const float c[3] = {-1.f + ((float)i + 0.5f) * dx, -1.f + ((float)j + 0.5f) * dx, -1.f + ((float)k + 0.5f) * dx};
-    const float dir[3] = {-1.f - c[0], -1.f - c[1], -1.f - c[2]};
+    float c[3], dir[3];
+    voxel_centre(tid, G, c, dir);
     const float* vb = vertices + (long long)b * V * 3;
     int hits = 0;
     float best = 1000.f;
     for (int f0 = 0; f0 < F; f0 += FT) {
         __syncthreads();
-        if (threadIdx.x < FT && f0 + (int)threadIdx.x < F) {
-            const int32_t* fc = faces + 3 * (f0 + threadIdx.x);
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                const float* vp = vb + 3 * fc[p];
-                tri[threadIdx.x][3 * p] = vp[0];
-                tri[threadIdx.x][3 * p + 1] = vp[1];
-                tri[threadIdx.x][3 * p + 2] = vp[2];
-            }
-        }
+        stage_faces(tri, faces, vb, f0, F);
         __syncthreads();
-        const int n = min(FT, F - f0);
-        if (live)
-            for (int f = 0; f < n; ++f) {
-                const float* t = tri[f];
-                float r[3], tt;
-                point_triangle(c, t, t + 3, t + 6, r);
-                best = fminf(best, dist3(c, r));
-                if (ray_triangle(c, dir, t, t + 3, t + 6, &tt) && tt >= 0.f) ++hits;
-            }
+        if (live) voxel_faces(tri, min(FT, F - f0), 0, 1, c, dir, best, hits);
     }
     if (live) phi[(long long)b * vox + tid] = (hits & 1) ? best : 0.f;
+}
+
+// The voxels list[b][0 .. count[b]) only (the ones a vertex of the other hand will sample, rih_two_hand_prep): a workgroup
+// takes SV = 64 of them and each of its four wavefronts every fourth face of a tile, so that one sample's few thousand
+// voxels spread over 4 x as many SIMDs as with a voxel per thread; the partial minima / counts meet in LDS in a fixed order.
+constexpr int SV = 64, SW = TPB / SV;
+
+__global__ __launch_bounds__(TPB) void sdf_sparse_kernel(float* __restrict__ phi, const int32_t* __restrict__ faces,
+                                                         const float* __restrict__ vertices, const int32_t* __restrict__ list,
+                                                         const int32_t* __restrict__ count, int max_count, int F, int V, int G) {
+    __shared__ float tri[FT][9];
+    __shared__ float sbest[SW - 1][SV];
+    __shared__ int shits[SW - 1][SV];
+    const int vox = G * G * G;
+    const int b = blockIdx.y;
+    const int nv = min(count[b], max_count);
+    if ((int)blockIdx.x * SV >= nv) return;                      // the whole workgroup: the grid is sized for the worst case
+    const int lane = threadIdx.x % SV, w = threadIdx.x / SV;
+    const int slot = blockIdx.x * SV + lane;
+    const bool live = slot < nv;
+    int tid = live ? list[(long long)b * max_count + slot] : 0;
+    if (tid < 0 || tid >= vox) tid = 0;
+    float c[3], dir[3];
+    voxel_centre(tid, G, c, dir);
+    const float* vb = vertices + (long long)b * V * 3;
+    int hits = 0;
+    float best = 1000.f;
+    for (int f0 = 0; f0 < F; f0 += FT) {
+        __syncthreads();
+        stage_faces(tri, faces, vb, f0, F);
+        __syncthreads();
+        if (live) voxel_faces(tri, min(FT, F - f0), w, SW, c, dir, best, hits);
+    }
+    if (w > 0) { sbest[w - 1][lane] = best; shits[w - 1][lane] = hits; }
+    __syncthreads();
+    if (w == 0 && live) {
+#pragma unroll
+        for (int q = 0; q < SW - 1; ++q) { best = fminf(best, sbest[q][lane]); hits += shits[q][lane]; }
+        phi[(long long)b * vox + tid] = (hits & 1) ? best : 0.f;
+    }
 }
 
 }  // namespace
@@ -129,5 +187,15 @@ extern "C" int rih_sdf(float* phi, const int32_t* faces, const float* vertices, 
     const long long vox = (long long)G * G * G;
     hipLaunchKernelGGL(sdf_kernel, dim3((unsigned)((vox + TPB - 1) / TPB), B), dim3(TPB), 0, (hipStream_t)stream, phi, faces,
                        vertices, F, V, G);
+    return (int)hipGetLastError();
+}
+
+extern "C" int rih_sdf_sparse(float* phi, const int32_t* faces, const float* vertices, const int32_t* list, const int32_t* count,
+                              int max_count, int B, int F, int V, int G, void* stream) {
+    if (!phi || !faces || !vertices || !list || !count || B < 1 || B > 65535 || F < 1 || V < 3 || G < 2 || G > 1024 ||
+        max_count < 1 || max_count > (long long)G * G * G)
+        return RIH_EINVAL;
+    hipLaunchKernelGGL(sdf_sparse_kernel, dim3((unsigned)((max_count + SV - 1) / SV), B), dim3(TPB), 0, (hipStream_t)stream,
+                       phi, faces, vertices, list, count, max_count, F, V, G);
     return (int)hipGetLastError();
 }
