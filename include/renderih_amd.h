@@ -508,6 +508,38 @@ int rih_mano_bwd(const rih_mano_model* m, const float* packed, const float* root
                  float* d_scale, float* ws_bwd, int B, void* stream);
 int64_t rih_mano_bwd_ws_floats(int B);
 
+/* Quaternion mode of the same kernels (ABI 23): manopth's ManoLayer as the pose optimiser builds it
+ * (pose_data_optimize/manopth/manopth/manolayer.py:235-250,258-380 with joint_rot_mode = root_rot_mode = 'quat';
+ * renderih_amd.quat_mano.FusedQuatManoLayer).  quat[B][16][4] in (w, x, y, z) order, root first, NOT normalised: R = the ceres
+ * form / |q|^2 (quatutils.py:168-221, no epsilon); left != 0 negates y and z first (the left hand).  The model's comps and
+ * hands_mean are not read (may be NULL); `packed` is rih_mano_pack's buffer, unchanged.  shape_stride = 10 (shape[B][10]) or 0
+ * (one vector of 10 shared by the batch).  tips: host array of the 5 finger-tip vertices of this call (a tip outside the
+ * packed buffer's compact copy reads its basis columns from the big matrix).  center_idx -1..20: -1 = nothing subtracted; the
+ * caller passes -1 together with trans (manopth centres only without a translation).
+ * rih_mano_quat_fwd: ONE launch (the conversion is the front end of the fused forward).  Outputs v[B][778][3], j[B][21][3]
+ *   (the 16 posed joints + 5 tips, reordered) and, unless NULL, transf[B][16][4][4] = [R_global | posed joint - centre + trans;
+ *   0 0 0 1].  ws as in rih_mano_fwd.
+ * rih_mano_quat_bwd: three launches, no atomics, fixed summation order.  Upstream dv[B][778][3], dj[B][21][3],
+ *   dtransf[B][16][4][4] (each may be NULL = zero); d_quat[B][16][4] includes the term of the division by |q|^2; d_shape[B][10]
+ *   and d_trans[B][3] may be NULL.  ws_bwd as in rih_mano_bwd (required).
+ * RIH_EINVAL: a null pointer that is not optional, B < 1, center_idx outside -1..20, a tip outside 0..777, another stride. */
+int rih_mano_quat_fwd(const rih_mano_model* m, const float* packed, const float* quat, int left, const float* shape,
+                      int shape_stride, const float* trans, int center_idx, const int32_t* tips, float* v, float* j,
+                      float* transf, float* ws, int B, void* stream);
+int rih_mano_quat_bwd(const rih_mano_model* m, const float* packed, const float* quat, int left, int center_idx,
+                      const int32_t* tips, const float* dv, const float* dj, const float* dtransf, const float* ws,
+                      float* d_quat, float* d_shape, float* d_trans, float* ws_bwd, int B, void* stream);
+
+/* Contact anchors (manopth/anchorutils.py:51-65; csrc/rih_anchor.hip, ABI 23): anchors[b][a] = w1 (v1 - v0) + w2 (v2 - v0) + v0
+ * over the vertices face_vert_idx[a][0..2] of vertices[B][V][3], weight[A][2].  Backward: g_vertices[B][V][3] gathered per
+ * vertex through vptr[V+1] / vlist[3A] (entries anchor * 3 + corner, ascending), which the HOST builds and range-checks once
+ * per index tensor; vertices that no anchor reads get exact zeros.  One launch each, no atomics.
+ * RIH_EINVAL: a null pointer, B < 1, V < 1, A < 1. */
+int rih_anchor_fwd(const float* vertices, const int32_t* face_vert_idx, const float* weight, float* anchors, int B, int V,
+                   int A, void* stream);
+int rih_anchor_bwd(const float* g_anchors, const int32_t* vptr, const int32_t* vlist, const float* weight, float* g_vertices,
+                   int B, int V, int A, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused mesh loss   (core/Loss.py:68-164 GraphLoss.calc_loss, :201-277 calc_loss_GCN; aux loss disabled there)
  * Constant topology of one hand (device pointers, uploaded once by the caller):
@@ -566,7 +598,7 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 22
+#define RIH_ABI_VERSION 23
 #define RIH_ABI_NSIZES 12
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);

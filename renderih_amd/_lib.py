@@ -201,6 +201,12 @@ SIGNATURES = {
                            C.c_void_p]),
     'rih_mano_bwd': (c_i, [C.POINTER(ManoModel), c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_i, c_f, c_f, c_f,
                            c_f, c_f, c_f, c_f, c_f, c_f, c_i, C.c_void_p]),
+    'rih_mano_quat_fwd': (c_i, [C.POINTER(ManoModel), c_f, c_f, c_i, c_f, c_i, c_f, c_i, C.POINTER(C.c_int32), c_f, c_f, c_f, c_f,
+                                c_i, C.c_void_p]),
+    'rih_mano_quat_bwd': (c_i, [C.POINTER(ManoModel), c_f, c_f, c_i, c_i, C.POINTER(C.c_int32), c_f, c_f, c_f, c_f, c_f, c_f, c_f,
+                                c_f, c_i, C.c_void_p]),
+    'rih_anchor_fwd': (c_i, [c_f, C.c_void_p, c_f, c_f, c_i, c_i, c_i, C.c_void_p]),
+    'rih_anchor_bwd': (c_i, [c_f, C.c_void_p, C.c_void_p, c_f, c_f, c_i, c_i, c_i, C.c_void_p]),
     'rih_mesh_loss': (c_i, [C.POINTER(MeshTopo), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_fl,
                             c_f, c_f, c_f, c_f, c_f, c_i, C.c_void_p]),
     'rih_mesh_loss_final': (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, C.c_void_p]),
@@ -227,7 +233,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 22     # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 23     # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 

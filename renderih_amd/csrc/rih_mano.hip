@@ -112,6 +112,52 @@ __device__ __forceinline__ void rodrigues_bwd(const float* ax, const float* D, f
     for (int k = 0; k < 3; ++k) dax[k] = da[k] / th + coef * ax[k];
 }
 
+// ---- quaternion mode (manopth's ManoLayer as the pose optimiser calls it; rih_mano_quat_fwd / rih_mano_quat_bwd) ----------------
+// The quaternion (w, x, y, z) is NOT normalised: R = ceres form / |q|^2 (manopth quatutils.py:168-221, no epsilon).  sgn = -1
+// negates y and z first (the left hand, manolayer.py:242-245).
+struct QuatFwd {
+    float sgn;              // +1 right, -1 left
+    int sstride;            // floats between the betas of consecutive hands: 10, or 0 = one vector shared by the batch
+    int tip[5];             // finger-tip vertices of this call (thumb .. pinky)
+    float* transf;          // [B][16][4][4] or NULL
+};
+struct QuatBwd {
+    int tip[5];
+    const float* dT;        // upstream gradient of transf [B][16][4][4] or NULL
+};
+template <typename A>
+__device__ __forceinline__ int quat_tip(const A& a, int q) {      // (selects: no dynamic index into a kernel argument)
+    return q == 0 ? a.tip[0] : q == 1 ? a.tip[1] : q == 2 ? a.tip[2] : q == 3 ? a.tip[3] : a.tip[4];
+}
+__device__ __forceinline__ void quat_fwd(const float* q, float sgn, float* R) {
+    const float w = q[0], x = q[1], y = sgn * q[2], z = sgn * q[3];
+    const float ww = w * w, wx = w * x, wy = w * y, wz = w * z, xx = x * x, xy = x * y, xz = x * z, yy = y * y, yz = y * z,
+                zz = z * z;
+    const float n2 = ww + xx + yy + zz;
+    R[0] = (ww + xx - yy - zz) / n2; R[1] = (2.f * (xy - wz)) / n2;   R[2] = (2.f * (wy + xz)) / n2;
+    R[3] = (2.f * (wz + xy)) / n2;   R[4] = (ww - xx + yy - zz) / n2; R[5] = (2.f * (yz - wx)) / n2;
+    R[6] = (2.f * (xz - wy)) / n2;   R[7] = (2.f * (wx + yz)) / n2;   R[8] = (ww - xx - yy + zz) / n2;
+}
+// dq_k = (sum_ij D_ij dN_ij/dq_k - 2 q_k sum_ij D_ij R_ij) / |q|^2 with N = the ceres numerators; the second term is what the
+// division by |q|^2 contributes (zero for D tangent to the rotation group at a unit quaternion, not in general)
+__device__ __forceinline__ void quat_bwd(const float* q, float sgn, const float* D, float* dq) {
+    float R[9];
+    quat_fwd(q, sgn, R);
+    const float w = q[0], x = q[1], y = sgn * q[2], z = sgn * q[3];
+    const float n2 = w * w + x * x + y * y + z * z;
+    float dr = 0.f;
+#pragma unroll
+    for (int e = 0; e < 9; ++e) dr += D[e] * R[e];
+    const float gw = 2.f * (w * (D[0] + D[4] + D[8]) + x * (D[7] - D[5]) + y * (D[2] - D[6]) + z * (D[3] - D[1]));
+    const float gx = 2.f * (x * (D[0] - D[4] - D[8]) + y * (D[1] + D[3]) + z * (D[2] + D[6]) + w * (D[7] - D[5]));
+    const float gy = 2.f * (y * (D[4] - D[0] - D[8]) + x * (D[1] + D[3]) + w * (D[2] - D[6]) + z * (D[5] + D[7]));
+    const float gz = 2.f * (z * (D[8] - D[0] - D[4]) + w * (D[3] - D[1]) + x * (D[2] + D[6]) + y * (D[5] + D[7]));
+    dq[0] = (gw - 2.f * w * dr) / n2;
+    dq[1] = (gx - 2.f * x * dr) / n2;
+    dq[2] = sgn * ((gy - 2.f * y * dr) / n2);
+    dq[3] = sgn * ((gz - 2.f * z * dr) / n2);
+}
+
 // ------------------------------------------------------------------------------------------------ forward A
 __global__ __launch_bounds__(256) void mano_pose_kernel(Model m, const float* __restrict__ root,
                                                         const float* __restrict__ pose, int ncomp,
@@ -488,14 +534,16 @@ constexpr int FUSED_LDS_FLOATS = KP * 192 + HC * LDPF + HC * GST + HC * SCR + 52
 static_assert(FUSED_LDS_FLOATS * 4 <= 163840, "LDS budget");
 static_assert(HC * 192 <= HC * SCR, "the v_tpose tile aliases the phase-1 scratch");
 
-template <bool HM>
+// QUAT: the quaternion front end of rih_mano_quat_fwd -- `pose` holds [B][16][4] quaternions (root included, `root` unused),
+// the tips come from qa.tip, the betas may be shared, and the 16 global transforms are written after centring / translation.
+template <bool HM, bool QUAT = false>
 __global__ __launch_bounds__(256) void mano_fused_kernel(Model m, const float* __restrict__ pk,
                                                          const float* __restrict__ root, const float* __restrict__ pose,
                                                          int ncomp, const float* __restrict__ shape,
                                                          const float* __restrict__ trans, const float* __restrict__ scale,
                                                          int center_idx, int new_skel, float* __restrict__ vout,
                                                          float* __restrict__ jout, float* __restrict__ ws, int B,
-                                                         long long* __restrict__ dbg) {
+                                                         long long* __restrict__ dbg, QuatFwd qa) {
     __shared__ __attribute__((aligned(16))) float smem[FUSED_LDS_FLOATS];
     // phase timestamps (shader clock) of the first chunk of the workgroups (tile, group 0): development aid, dbg == NULL otherwise
 #define RIH_STAMP(i_) do { if (dbg != nullptr && threadIdx.x == 0 && blockIdx.y == 0 && chunk == 0) dbg[blockIdx.x * 16 + (i_)] = clock64(); } while (0)
@@ -543,6 +591,12 @@ __global__ __launch_bounds__(256) void mano_fused_kernel(Model m, const float* _
         float bv_sp[KP / 4];
         if (need_special && wave < 3) {
             const int kq = lane >> 4, n = wave * 16 + (lane & 15);
+            if (QUAT) {         // a tip that is not in the compact copy (the left hand's 445) comes from the big matrix
+                int base = PK_SP + n, ld = 48;
+                if (n < 15 && quat_tip(qa, n / 3) != c_special[n / 3]) { base = quat_tip(qa, n / 3) * 3 + n % 3; ld = NCP; }
+#pragma unroll
+                for (int ks = 0; ks < KP / 4; ++ks) bv_sp[ks] = pk[base + (4 * ks + kq) * ld];
+            } else
 #pragma unroll
             for (int ks = 0; ks < KP / 4; ++ks) bv_sp[ks] = pk[PK_SP + (4 * ks + kq) * 48 + n];       // (compact copy: rih_mano_pack)
         }
@@ -569,7 +623,7 @@ __global__ __launch_bounds__(256) void mano_fused_kernel(Model m, const float* _
         for (int i = t; i < HC * 13; i += 256) {
             const int hl = i / 13, e = i - hl * 13, h = h0 + hl;
             float x = 0.f;
-            if (h < B) x = (e < 10) ? shape[h * 10 + e] : (e == 10 ? 1.f : 0.f);
+            if (h < B) x = (e < 10) ? shape[h * (QUAT ? qa.sstride : 10) + e] : (e == 10 ? 1.f : 0.f);
             s_pf[hl * LDPF + NPF + e] = x;
         }
         __syncthreads();
@@ -589,7 +643,9 @@ __global__ __launch_bounds__(256) void mano_fused_kernel(Model m, const float* _
             const int hl = t >> 4, j = t & 15, h = h0 + hl;
             float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
             if (h < B) {
-                if (j == 0) {
+                if (QUAT) {
+                    quat_fwd(pose + ((long long)h * NJ + j) * 4, qa.sgn, R);
+                } else if (j == 0) {
                     for (int e = 0; e < 9; ++e) R[e] = root[(long long)h * 9 + e];
                 } else if (ncomp > 0) {
                     rodrigues_fwd(&s_scr[hl * SCR + S_AX + (j - 1) * 3], R);
@@ -668,7 +724,7 @@ __global__ __launch_bounds__(256) void mano_fused_kernel(Model m, const float* _
             __syncthreads();
             RIH_STAMP2(1);
             for (int i = t; i < HC * 13; i += 256) {
-                const int hl = i / 13, q = i - hl * 13, vv = c_special[q];
+                const int hl = i / 13, q = i - hl * 13, vv = (QUAT && q < 5) ? quat_tip(qa, q) : c_special[q];
                 // the vertex's sixteen weights in four 16-byte requests up front (the joint loop used to wait for one dword load
                 // per joint: sixteen L2 round trips in a row, most of the 20 k cycles this phase took), the SE3s as 16-byte LDS reads
                 float wv[NJ];
@@ -736,6 +792,16 @@ __global__ __launch_bounds__(256) void mano_fused_kernel(Model m, const float* _
                 for (int i = t; i < HC * GST; i += 256) {
                     const int hl = i / GST, e = i - hl * GST, h = h0 + hl;
                     if (h < B) ws[(long long)h * WS_STRIDE + OFF_G + e] = s_G[i];     // OFF_POST = OFF_G + 192
+                }
+            if (QUAT && qa.transf != nullptr)       // manopth's transforms: [R_global | posed joint - centre + trans; 0 0 0 1]
+                for (int i = t; i < HC * 256; i += 256) {
+                    const int hl = i >> 8, e = i & 255, h = h0 + hl, j = e >> 4, r = (e >> 2) & 3, c = e & 3;
+                    if (h >= B) continue;
+                    const float* post = &s_G[hl * GST + 192];
+                    float o = (c == 3) ? 1.f : 0.f;
+                    if (r < 3) o = (c < 3) ? s_G[hl * GST + j * 12 + r * 4 + c]
+                                           : (s_scr[hl * SCR + S_SRC + j * 3 + r] - post[r]) * post[3] + post[4 + r];
+                    qa.transf[(long long)h * 256 + e] = o;
                 }
             __syncthreads();            // the scratch (src / sp) is overwritten by the v_tpose tile below
         }
@@ -945,13 +1011,16 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
     return red[0] + red[1] + red[2] + red[3];
 }
 
+// QUAT (rih_mano_quat_bwd): dv / dj may be NULL (zero), qb.dT adds the transforms' upstream gradient -- rotation part onto dG
+// before it goes up the tree, translation part onto the chain joints and the centre / translation sums --, tips from qb.tip
+template <bool QUAT = false>
 __global__ __launch_bounds__(256) void mano_bwd_kernel(Model m, const float* __restrict__ pose, int ncomp,
                                                        int center_idx, int new_skel, int has_scale,
                                                        const float* __restrict__ dv, const float* __restrict__ dj,
                                                        const float* __restrict__ ws, float* __restrict__ d_root,
                                                        float* __restrict__ d_pose, float* __restrict__ d_shape,
                                                        float* __restrict__ d_trans, float* __restrict__ d_scale,
-                                                       float* __restrict__ wsb, long long* __restrict__ dbg) {
+                                                       float* __restrict__ wsb, long long* __restrict__ dbg, QuatBwd qb) {
     // phase timestamps of workgroup 0 (development aid, tools/mano_phases.py): slots 208.. of the rih_mano_debug_stamps buffer
 #define RIH_BSTAMP(i_) do { if (dbg != nullptr && threadIdx.x == 0 && blockIdx.x == 0) dbg[208 + (i_)] = clock64(); } while (0)
     RIH_BSTAMP(0);
@@ -975,12 +1044,15 @@ __global__ __launch_bounds__(256) void mano_bwd_kernel(Model m, const float* __r
     const float* w = (const float*)__builtin_assume_aligned(ws + (long long)b * WS_STRIDE, 16);     // (WS_STRIDE % 4 == 0)
     const float* dvb = dv + (long long)b * NVC;
     const float* djb = dj + (long long)b * 63;
+    const bool has_dv = !QUAT || dv != nullptr, has_dj = !QUAT || dj != nullptr;
+    __shared__ float s_dT[QUAT ? NJ * 12 : 1];     // QUAT: the hand's d transf, rows 0..2 (the bottom row is constant)
+    if (QUAT && t < NJ * 12) s_dT[t] = (qb.dT != nullptr) ? qb.dT[(long long)b * 256 + (t / 12) * 16 + t % 12] : 0.f;
 
     if (t < NJ * 12) { s_G[t] = w[OFF_G + t]; s_dG[t] = 0.f; }
     if (t < NJ * 9) { s_R[t] = w[OFF_R + t]; s_dR[t] = 0.f; }
     if (t < NJ * 3) { s_jt[t] = w[OFF_JT + t]; s_djt[t] = 0.f; }
     if (t < 63) {
-        float d = djb[t];
+        float d = has_dj ? djb[t] : 0.f;
         if (new_skel) {
             const int k = t / 3;
             if (k == 5 || k == 9 || k == 13 || k == 17) d = 0.f;
@@ -1003,7 +1075,7 @@ __global__ __launch_bounds__(256) void mano_bwd_kernel(Model m, const float* __r
 #pragma unroll
         for (int u = 0; u < NIT; ++u) {
             const int i = t + 256 * u;
-            dreg[u] = (i < NVC) ? dvb[i] : 0.f;
+            dreg[u] = (i < NVC && has_dv) ? dvb[i] : 0.f;
             wreg[u] = (i < NVC) ? w[OFF_VSC + i] : 0.f;
         }
 #pragma unroll
@@ -1040,6 +1112,8 @@ __global__ __launch_bounds__(256) void mano_bwd_kernel(Model m, const float* __r
     }
     float sj[3] = {0.f, 0.f, 0.f};
     for (int k = 0; k < 21; ++k) { sj[0] += s_djeff[k * 3]; sj[1] += s_djeff[k * 3 + 1]; sj[2] += s_djeff[k * 3 + 2]; }
+    if (QUAT)
+        for (int k = 0; k < NJ; ++k) { sj[0] += s_dT[k * 12 + 3]; sj[1] += s_dT[k * 12 + 7]; sj[2] += s_dT[k * 12 + 11]; }
     const float st[3] = {sv0 + sj[0], sv1 + sj[1], sv2 + sj[2]};
     if (t == 0) {
         if (d_trans) for (int c = 0; c < 3; ++c) d_trans[b * 3 + c] = st[c];
@@ -1051,6 +1125,7 @@ __global__ __launch_bounds__(256) void mano_bwd_kernel(Model m, const float* __r
         const int k = t / 3, c = t % 3;
         float d = sc * s_djeff[t];
         if (center_idx >= 0 && k == center_idx) d -= sc * st[c];
+        if (QUAT && c_new_order[k] < NJ) d += s_dT[c_new_order[k] * 12 + c * 4 + 3];
         s_dsrc[c_new_order[k] * 3 + c] = d;
     }
     __syncthreads();
@@ -1084,7 +1159,7 @@ __global__ __launch_bounds__(256) void mano_bwd_kernel(Model m, const float* __r
                 float x = sc * s_dvs[v * 3 + c];
 #pragma unroll
                 for (int q = 0; q < 5; ++q)
-                    if (c_special[q] == v) x += s_dsrc[(16 + q) * 3 + c];
+                    if ((QUAT ? quat_tip(qb, q) : c_special[q]) == v) x += s_dsrc[(16 + q) * 3 + c];
                 d[vi][c] = x;
             }
         }
@@ -1168,6 +1243,7 @@ __global__ __launch_bounds__(256) void mano_bwd_kernel(Model m, const float* __r
             const int i = s_child[q];
             a += s_dsrc[i * 3 + r] * (c < 3 ? s_jt[i * 3 + c] : 1.f);
         }
+        if (QUAT && c < 3) a += s_dT[t];
         s_dG[t] += a;
     } else if (t < NJ * 12 + NJ * 3) {
         const int i = (t - NJ * 12) / 3, c = (t - NJ * 12) - i * 3;
@@ -1416,10 +1492,13 @@ __global__ __launch_bounds__(256) void mano_bwd_blend_kernel(const float* __rest
 // (First version of this round: a workgroup per 16 hands looping ten times over 13 requests, then 45-step loops on global
 // memory -- 24 us for 8 workgroups, 28 us for 256: a chain of round trips.)
 constexpr int FH = 4;
+// QUAT: d_pose receives the quaternion gradients [B][16][4] of all sixteen rotations (quat_bwd), `quat` = the forward's input
+template <bool QUAT = false>
 __global__ __launch_bounds__(256) void mano_bwd_finish_kernel(Model m, const float* __restrict__ pk, int ncomp,
                                                               const float* __restrict__ pose, const float* __restrict__ wsb,
                                                               const float* __restrict__ part,
-                                                              float* __restrict__ d_pose, float* __restrict__ d_shape, int B) {
+                                                              float* __restrict__ d_pose, float* __restrict__ d_shape, int B,
+                                                              const float* __restrict__ quat, float sgn) {
     __shared__ float s_comps[45 * 45], s_js[480];
     __shared__ float s_dR[FH][144], s_ax[FH][48], s_dax[FH][48], s_djt[FH][48], s_out[FH][BL_ROWS], s_pose[FH][48];
     const int t = threadIdx.x, lane = t & 63, hl = t >> 6, h = blockIdx.x * FH + hl;
@@ -1479,7 +1558,9 @@ __global__ __launch_bounds__(256) void mano_bwd_finish_kernel(Model m, const flo
         if (e < NPF) s_dR[hl][9 + e] += s_out[hl][e];
     }
     __syncthreads();
-    if (ncomp > 0) {
+    if (QUAT) {
+        if (lane < NJ && live) quat_bwd(quat + ((long long)h * NJ + lane) * 4, sgn, &s_dR[hl][lane * 9], d_pose + ((long long)h * NJ + lane) * 4);
+    } else if (ncomp > 0) {
         if (lane < 15) rodrigues_bwd(&s_ax[hl][lane * 3], &s_dR[hl][(lane + 1) * 9], &s_dax[hl][lane * 3]);
         __syncthreads();
         if (lane < ncomp && live) {
@@ -1567,13 +1648,13 @@ extern "C" int rih_mano_fwd(const rih_mano_model* m, const float* packed, const 
         if (variant == 2 || (variant == 0 && nchunks >= 256)) {
             // hand-chunk major: the pose work of a chunk once, basis tiles streamed from L2 (one workgroup per CU: LDS)
             hipLaunchKernelGGL(mano_fused_kernel<true>, dim3(nchunks < 256 ? nchunks : 256), dim3(256), 0, s, mm, packed, root,
-                               pose, ncomp, shape, trans, scale, center_idx, new_skel, v, j, ws, B, g_mano_dbg);
+                               pose, ncomp, shape, trans, scale, center_idx, new_skel, v, j, ws, B, g_mano_dbg, QuatFwd{});
             return (int)hipGetLastError();
         }
         int groups = (512 + NTILES - 1) / NTILES;
         if (groups > nchunks) groups = nchunks;
         hipLaunchKernelGGL(mano_fused_kernel<false>, dim3(NTILES, groups), dim3(256), 0, s, mm, packed, root, pose, ncomp,
-                           shape, trans, scale, center_idx, new_skel, v, j, ws, B, g_mano_dbg);
+                           shape, trans, scale, center_idx, new_skel, v, j, ws, B, g_mano_dbg, QuatFwd{});
         return (int)hipGetLastError();
     }
     if (variant != 1 || !ws) return RIH_EINVAL;     // round-1 two-kernel forward (A/B timing): needs the workspace
@@ -1602,8 +1683,8 @@ extern "C" int rih_mano_bwd(const rih_mano_model* m, const float* packed, const 
     const Model mm = to_model(m);
     hipStream_t s = (hipStream_t)stream;
     // ws_bwd == NULL: the one-kernel backward of round 1 (one workgroup per hand does everything; kept for A/B timing)
-    hipLaunchKernelGGL(mano_bwd_kernel, dim3(B), dim3(256), 0, s, mm, pose, ncomp, center_idx, new_skel, scale ? 1 : 0, dv, dj,
-                       ws, d_root, d_pose, d_shape, d_trans, d_scale, ws_bwd, g_mano_dbg);
+    hipLaunchKernelGGL(mano_bwd_kernel<false>, dim3(B), dim3(256), 0, s, mm, pose, ncomp, center_idx, new_skel, scale ? 1 : 0, dv, dj,
+                       ws, d_root, d_pose, d_shape, d_trans, d_scale, ws_bwd, g_mano_dbg, QuatBwd{});
     if (ws_bwd != nullptr && (d_pose != nullptr || d_shape != nullptr)) {
         const int nchunks = (B + HC - 1) / HC;
         // 13 tiles x groups of chunks: as many groups as keep the launch within one workgroup per CU (LDS: one fits) -- 19 on
@@ -1617,8 +1698,72 @@ extern "C" int rih_mano_bwd(const rih_mano_model* m, const float* packed, const 
         if (groups > nchunks) groups = nchunks;
         float* part = ws_bwd + (long long)B * BW_STRIDE;
         hipLaunchKernelGGL(mano_bwd_blend_kernel, dim3(NTILES, groups), dim3(256), 0, s, packed, ws_bwd, part, B);
-        hipLaunchKernelGGL(mano_bwd_finish_kernel, dim3((B + FH - 1) / FH), dim3(256), 0, s, mm, packed, ncomp, pose, ws_bwd, part,
-                           d_pose, d_shape, B);
+        hipLaunchKernelGGL(mano_bwd_finish_kernel<false>, dim3((B + FH - 1) / FH), dim3(256), 0, s, mm, packed, ncomp, pose, ws_bwd, part,
+                           d_pose, d_shape, B, (const float*)nullptr, 1.f);
     }
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------ quaternion mode
+static bool quat_args_ok(const rih_mano_model* m, const float* packed, const float* quat, int center_idx, const int32_t* tips, int B) {
+    if (!m || !m->shapedirs || !m->posedirs || !m->v_template || !m->J_reg || !m->weights) return false;
+    if (m->parent[0] >= 0) return false;
+    for (int i = 1; i < 16; ++i)
+        if (m->parent[i] < 0 || m->parent[i] >= i) return false;
+    if (!packed || ((uintptr_t)packed % 16) != 0 || !quat || !tips || B < 1 || center_idx < -1 || center_idx > 20) return false;
+    for (int q = 0; q < 5; ++q)
+        if (tips[q] < 0 || tips[q] >= NV) return false;
+    return true;
+}
+
+extern "C" int rih_mano_quat_fwd(const rih_mano_model* m, const float* packed, const float* quat, int left, const float* shape,
+                                 int shape_stride, const float* trans, int center_idx, const int32_t* tips, float* v, float* j,
+                                 float* transf, float* ws, int B, void* stream) {
+    if (!quat_args_ok(m, packed, quat, center_idx, tips, B) || !shape || !v || !j) return RIH_EINVAL;
+    if (shape_stride != 0 && shape_stride != 10) return RIH_EINVAL;
+    const Model mm = to_model(m);
+    hipStream_t s = (hipStream_t)stream;
+    QuatFwd qa;
+    qa.sgn = left ? -1.f : 1.f;
+    qa.sstride = shape_stride;
+    for (int q = 0; q < 5; ++q) qa.tip[q] = tips[q];
+    qa.transf = transf;
+    const float* no_root = nullptr;
+    const float* no_scale = nullptr;
+    // always tile major: the optimiser's batches are far below the 4096 hands from which rih_mano_fwd goes hand-chunk major
+    const int nchunks = (B + HC - 1) / HC;
+    int groups = (512 + NTILES - 1) / NTILES;
+    if (groups > nchunks) groups = nchunks;
+    auto kern = mano_fused_kernel<false, true>;
+    hipLaunchKernelGGL(kern, dim3(NTILES, groups), dim3(256), 0, s, mm, packed, no_root, quat, 0, shape, trans, no_scale,
+                       center_idx, 0, v, j, ws, B, g_mano_dbg, qa);
+    return (int)hipGetLastError();
+}
+
+extern "C" int rih_mano_quat_bwd(const rih_mano_model* m, const float* packed, const float* quat, int left, int center_idx,
+                                 const int32_t* tips, const float* dv, const float* dj, const float* dtransf, const float* ws,
+                                 float* d_quat, float* d_shape, float* d_trans, float* ws_bwd, int B, void* stream) {
+    if (!quat_args_ok(m, packed, quat, center_idx, tips, B) || !ws || !d_quat || !ws_bwd) return RIH_EINVAL;
+    if (((uintptr_t)ws & 15) || ((uintptr_t)ws_bwd & 15)) return RIH_EINVAL;
+    const Model mm = to_model(m);
+    hipStream_t s = (hipStream_t)stream;
+    QuatBwd qb;
+    for (int q = 0; q < 5; ++q) qb.tip[q] = tips[q];
+    qb.dT = dtransf;
+    float* none = nullptr;
+    hipLaunchKernelGGL(mano_bwd_kernel<true>, dim3(B), dim3(256), 0, s, mm, quat, 0, center_idx, 0, 0, dv, dj, ws, none, none,
+                       d_shape, d_trans, none, ws_bwd, g_mano_dbg, qb);
+    const int nchunks = (B + HC - 1) / HC;
+    int cus = 0, dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus < 1)
+        cus = 256;
+    int groups = cus / NTILES;
+    if (groups < 1) groups = 1;
+    if (groups > nchunks) groups = nchunks;
+    float* part = ws_bwd + (long long)B * BW_STRIDE;
+    hipLaunchKernelGGL(mano_bwd_blend_kernel, dim3(NTILES, groups), dim3(256), 0, s, packed, ws_bwd, part, B);
+    hipLaunchKernelGGL(mano_bwd_finish_kernel<true>, dim3((B + FH - 1) / FH), dim3(256), 0, s, mm, packed, 0, quat, ws_bwd, part,
+                       d_quat, d_shape, B, quat, left ? -1.f : 1.f);
     return (int)hipGetLastError();
 }
