@@ -540,6 +540,34 @@ int rih_anchor_fwd(const float* vertices, const int32_t* face_vert_idx, const fl
 int rih_anchor_bwd(const float* g_anchors, const int32_t* vptr, const int32_t* vlist, const float* weight, float* g_vertices,
                    int B, int V, int A, void* stream);
 
+/* Hand-prior and contact terms of the pose optimiser's two-hand objective (hocontact/postprocess/geo_loss.py:
+ * batch_pose_quat_norm_loss, edge_len_loss, hand_pose_ergonomics_loss, FieldLoss.batch_contact_loss, summed as
+ * geo_optimizer_both_batch.py:805-824 does for mode='both'; csrc/rih_pose_prior.hip, ABI 24;
+ * renderih_amd.pose_prior.FusedTwoHandPriorLoss builds every constant).  Index 0 / suffix _r is the right (main) hand, 1 / _l
+ * the left (sub) hand.
+ * rih_pose_prior_fwd (one launch, one workgroup per (sample, hand)): q_*[B][16][4] (w, x, y, z), NOT normalised;
+ *   verts_*[B][V][3]; anchors_*[B][A][3].  joint_tables[2][15][18]: per hand and finger joint the 3x3 matrices Lm, Rm with
+ *   relative frame = Lm R(q) Rm.  edges[E][2] (both hands), static_len[2][E]; vptr[V+1] / vlist[2E] (entries edge * 2 + end,
+ *   ascending): the vertex -> edge lists, built and range-checked by the HOST.  anchor_id[B][A][D] (indices into the MAIN
+ *   hand's anchors, range-checked by the host), elastic[B][A][D]; cptr[B][A+1] / clist[B][A*D] (entries i * D + d): per sample
+ *   the main anchor -> contact pair lists.  inv_mask_sum = 1 / mask.sum(), or 0 for an empty mask (contact term and its
+ *   gradients exactly 0).  Writes partial[B][2][4] (per sample and hand: quaternion norm, edge, ergonomics, contact -- the last
+ *   in the left hand's slot -- each already divided by its element count) and grads: the gradient of
+ *   norm_r + norm_l + edge_r + edge_l + lambda_contact * contact + ergo_r + ergo_l with respect to q_r, q_l, verts_r, verts_l,
+ *   anchors_r, anchors_l, back to back in that order (B * (128 + 6 V + 6 A) floats).  No atomics; a vertex without an edge
+ *   gets an exact zero.
+ * rih_pose_prior_reduce (one workgroup): terms[7] = the seven terms in the order above (contact without its weight), summed
+ *   over the batch in index order; loss[0] = their sum with lambda_contact applied.
+ * rih_pose_prior_bwd (elementwise): out[i] = grads[i] * grad_out[0] over n floats (grad_out: DEVICE scalar).
+ * RIH_EINVAL: a null pointer, B < 1 or > 65535, V, E, A, D or n < 1, a negative or NaN inv_mask_sum. */
+int rih_pose_prior_fwd(const float* q_r, const float* q_l, const float* verts_r, const float* verts_l, const float* anchors_r,
+                       const float* anchors_l, const float* joint_tables, const int32_t* edges, const float* static_len,
+                       const int32_t* vptr, const int32_t* vlist, const int32_t* anchor_id, const float* elastic,
+                       const int32_t* cptr, const int32_t* clist, float inv_mask_sum, float lambda_contact, float* grads,
+                       float* partial, int B, int V, int E, int A, int D, void* stream);
+int rih_pose_prior_reduce(const float* partial, float lambda_contact, float* terms, float* loss, int B, void* stream);
+int rih_pose_prior_bwd(const float* grads, const float* grad_out, float* out, int64_t n, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused mesh loss   (core/Loss.py:68-164 GraphLoss.calc_loss, :201-277 calc_loss_GCN; aux loss disabled there)
  * Constant topology of one hand (device pointers, uploaded once by the caller):
@@ -598,7 +626,7 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 23
+#define RIH_ABI_VERSION 24
 #define RIH_ABI_NSIZES 12
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);

@@ -207,6 +207,10 @@ SIGNATURES = {
                                 c_f, c_i, C.c_void_p]),
     'rih_anchor_fwd': (c_i, [c_f, C.c_void_p, c_f, c_f, c_i, c_i, c_i, C.c_void_p]),
     'rih_anchor_bwd': (c_i, [c_f, C.c_void_p, C.c_void_p, c_f, c_f, c_i, c_i, c_i, C.c_void_p]),
+    'rih_pose_prior_fwd': (c_i, [c_f] * 7 + [C.c_void_p, c_f, C.c_void_p, C.c_void_p, C.c_void_p, c_f, C.c_void_p, C.c_void_p,
+                                 c_fl, c_fl, c_f, c_f, c_i, c_i, c_i, c_i, c_i, C.c_void_p]),
+    'rih_pose_prior_reduce': (c_i, [c_f, c_fl, c_f, c_f, c_i, C.c_void_p]),
+    'rih_pose_prior_bwd': (c_i, [c_f, c_f, c_f, c_l, C.c_void_p]),
     'rih_mesh_loss': (c_i, [C.POINTER(MeshTopo), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_fl,
                             c_f, c_f, c_f, c_f, c_f, c_i, C.c_void_p]),
     'rih_mesh_loss_final': (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, C.c_void_p]),
@@ -233,7 +237,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 23     # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 24     # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 
