@@ -568,6 +568,45 @@ int rih_pose_prior_fwd(const float* q_r, const float* q_l, const float* verts_r,
 int rih_pose_prior_reduce(const float* partial, float lambda_contact, float* terms, float* loss, int B, void* stream);
 int rih_pose_prior_bwd(const float* grads, const float* grad_out, float* out, int64_t n, void* stream);
 
+/* Adam and the plateau scheduler of the pose optimiser with every scalar on the device (geo_optimizer_both_batch.py:428-432
+ * `torch.optim.Adam` + `ReduceLROnPlateau`, :879-880 `optimizer.step(); scheduler.step(loss)`; csrc/rih_pose_opt.hip, ABI 25;
+ * renderih_amd.pose_opt).  One optimiser iteration is rih_adam_dev then rih_plateau_step on the same stream, with no host read:
+ * the pair can be captured in a hipGraph and replayed.
+ * rih_opt_state (DEVICE memory, 8-byte aligned, filled by the host before the first step): `step` = iterations done (Adam's
+ *   bias corrections use step + 1), `best` (+inf at the start) and `num_bad_epochs` of the scheduler, one learning rate per
+ *   parameter group, and the scheduler's settings (mode 'min', threshold_mode 'rel', cooldown 0; one min_lr for all groups).
+ * rih_adam_dev (grid: chunks of 1024 elements x tensors): torch.optim.Adam (amsgrad off, no weight decay) over `ntensors`
+ *   table entries (DEVICE memory); max_n >= every entry's n sizes the grid.  The learning rate of entry.group and the step
+ *   count are read from `state`; bias corrections in double, on the device.  Element i of an entry is FROZEN when
+ *   period > 0 and (i % period) < skip: its p, m and v keep their bits.  prev (or NULL) receives p from before the step,
+ *   frozen elements included.  The kernel only reads `state`.
+ * rih_plateau_step (one workgroup): ReduceLROnPlateau.step(loss[0]) on `state`: better iff loss < best * (1 - threshold) in
+ *   double (a NaN loss is not better); otherwise num_bad_epochs += 1; when num_bad_epochs > patience every group's lr
+ *   becomes max(lr * factor, min_lr) if that lowers it by more than eps_lr, and num_bad_epochs = 0; then step += 1.
+ * RIH_EINVAL: a null pointer, ntensors < 1, max_n < 1, betas outside [0, 1), a negative or NaN eps. */
+#define RIH_OPT_MAX_GROUPS 8
+typedef struct rih_opt_state {
+    double best;
+    double lr[RIH_OPT_MAX_GROUPS];
+    double factor, threshold, min_lr, eps_lr;
+    int64_t step;
+    int32_t num_bad_epochs, patience, ngroups, reserved;
+} rih_opt_state;
+typedef struct rih_adam_dev_entry {
+    float* p;           /* parameter, updated in place */
+    const float* g;     /* gradient */
+    float* m;           /* exp_avg */
+    float* v;           /* exp_avg_sq */
+    float* prev;        /* NULL, or n floats: the parameter before this step */
+    int64_t n;          /* elements */
+    int32_t group;      /* index into rih_opt_state.lr, 0 <= group < ngroups */
+    int32_t period, skip;   /* frozen pattern; period = 0: none */
+    int32_t reserved;
+} rih_adam_dev_entry;
+int rih_adam_dev(const rih_adam_dev_entry* table, int ntensors, int64_t max_n, const rih_opt_state* state, float beta1,
+                 float beta2, float eps, void* stream);
+int rih_plateau_step(rih_opt_state* state, const float* loss, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused mesh loss   (core/Loss.py:68-164 GraphLoss.calc_loss, :201-277 calc_loss_GCN; aux loss disabled there)
  * Constant topology of one hand (device pointers, uploaded once by the caller):
@@ -624,10 +663,10 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
 /* library / device info.  RIH_ABI_VERSION is bumped whenever a struct layout or a signature of this header changes;
  * rih_version() returns the value the library was compiled with and rih_abi_sizes() the sizeof of EVERY by-pointer struct, in
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
- * conv3 desc, h2 desc, panel desc (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
+ * conv3 desc, h2 desc, panel desc, opt state, adam dev entry (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 24
-#define RIH_ABI_NSIZES 12
+#define RIH_ABI_VERSION 25
+#define RIH_ABI_NSIZES 14
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);
 const char* rih_arch(void);

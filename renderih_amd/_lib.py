@@ -92,6 +92,18 @@ class MeshTopo(C.Structure):
                 ('pool', C.c_int32)]
 
 
+class OptState(C.Structure):
+    """rih_opt_state: the device block of rih_adam_dev / rih_plateau_step."""
+    _fields_ = [('best', C.c_double), ('lr', C.c_double * 8), ('factor', C.c_double), ('threshold', C.c_double),
+                ('min_lr', C.c_double), ('eps_lr', C.c_double), ('step', C.c_int64), ('num_bad_epochs', C.c_int32),
+                ('patience', C.c_int32), ('ngroups', C.c_int32), ('reserved', C.c_int32)]
+
+
+class AdamDevEntry(C.Structure):
+    _fields_ = [('p', C.c_void_p), ('g', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p), ('prev', C.c_void_p),
+                ('n', C.c_int64), ('group', C.c_int32), ('period', C.c_int32), ('skip', C.c_int32), ('reserved', C.c_int32)]
+
+
 # name -> (restype, argtypes); must list every symbol include/renderih_amd.h declares
 SIGNATURES = {
     'rih_cdev': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, c_fl, c_f, C.c_void_p]),
@@ -211,6 +223,8 @@ SIGNATURES = {
                                  c_fl, c_fl, c_f, c_f, c_i, c_i, c_i, c_i, c_i, C.c_void_p]),
     'rih_pose_prior_reduce': (c_i, [c_f, c_fl, c_f, c_f, c_i, C.c_void_p]),
     'rih_pose_prior_bwd': (c_i, [c_f, c_f, c_f, c_l, C.c_void_p]),
+    'rih_adam_dev': (c_i, [C.c_void_p, c_i, c_l, C.c_void_p, c_fl, c_fl, c_fl, C.c_void_p]),
+    'rih_plateau_step': (c_i, [C.c_void_p, c_f, C.c_void_p]),
     'rih_mesh_loss': (c_i, [C.POINTER(MeshTopo), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_fl,
                             c_f, c_f, c_f, c_f, c_f, c_i, C.c_void_p]),
     'rih_mesh_loss_final': (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, C.c_void_p]),
@@ -237,7 +251,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 24     # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 25     # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 
@@ -270,11 +284,11 @@ def load():
         fn = getattr(lib, name)      # AttributeError => a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    # every by-pointer struct of the header, in rih_abi_sizes' order; the last one (rih_adam_entry: four pointers + int64) is
-    # built by hand as int64 rows in renderih_amd/optim.py
+    # every by-pointer struct of the header, in rih_abi_sizes' order; rih_adam_entry (four pointers + int64) is built by hand
+    # as int64 rows in renderih_amd/optim.py
     mine = [C.sizeof(GemmDesc), C.sizeof(ManoModel), C.sizeof(MeshTopo), C.sizeof(HConvDesc),
             C.sizeof(ReduceDesc), C.sizeof(PackDesc), C.sizeof(LnFinalDesc), 5 * 8, C.sizeof(AbsmaxDesc),
-            C.sizeof(Conv3Desc), C.sizeof(H2Desc), C.sizeof(PanelDesc)]
+            C.sizeof(Conv3Desc), C.sizeof(H2Desc), C.sizeof(PanelDesc), C.sizeof(OptState), C.sizeof(AdamDevEntry)]
     if lib.rih_version() != ABI_VERSION:
         raise RuntimeError('librenderih_amd.so does not match this binding (ABI %d vs %d): rebuild with '
                            '`python -m renderih_amd._build`' % (lib.rih_version(), ABI_VERSION))

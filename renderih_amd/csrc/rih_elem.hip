@@ -2003,6 +2003,8 @@ extern "C" int rih_abi_sizes(int32_t* out9) {      // RIH_ABI_NSIZES values
     out9[9] = (int32_t)sizeof(rih_conv3_desc);
     out9[10] = (int32_t)sizeof(rih_h2_desc);
     out9[11] = (int32_t)sizeof(rih_panel_desc);
+    out9[12] = (int32_t)sizeof(rih_opt_state);
+    out9[13] = (int32_t)sizeof(rih_adam_dev_entry);
     return 0;
 }
 extern "C" const char* rih_arch(void) { return "gfx950"; }
