@@ -276,9 +276,15 @@ int rih_panel(const rih_panel_desc* d, void* stream);
 /* Long-K plain-row GEMM (csrc/rih_conv3.hip rows_kernel, ABI 18) -- the 1x1 convolutions with K >= 256 of Bottleneck.conv1 / conv3
  * and their data gradients (torchvision Bottleneck via models/encoder.py:75-89,107-126): the same descriptor and the same
  * arithmetic as rih_panel (engine 2, H2 weight planes), as 512-thread workgroups on 256 x 128 / 128 x 128 / 256 x 64 / 128 x 64 tiles
- * with the weights staged by LDS-DMA and three A stages in LDS.  Preconditions (rih_rows_ok returns 1): K % 32 == 0, K >= 64,
- * N % 64 == 0, M % 128 == 0, pitches % 4 == 0, 16-byte aligned operands, M * lda * 4 < 2^31, not both stats and r.
- * stats (optional): [M / rows][2][N] per block of rows = rih_rows_stats_rows(desc) consecutive rows (64 or 32). */
+ * with the weights staged by LDS-DMA on three stages, two A stages in LDS and the A prefetch in registers.  Preconditions
+ * (rih_rows_ok returns 1): K % 32 == 0, K >= 64, N % 64 == 0, M % 128 == 0, pitches % 4 == 0, 16-byte aligned operands,
+ * M * lda * 4 < 2^31, not both stats and r.
+ * stats (optional): [M / rows][2][N] per block of rows = rih_rows_stats_rows(desc) consecutive rows (64 or 32).
+ * The tile is the library's choice (the largest that still gives every CU a workgroup).  ABI 26: rih_rows_tile reports that choice
+ * (returns 1; 0 with *bm / *bn untouched when rih_rows_ok is 0) and rih_rows_tiled is the same launch on a tile the caller names --
+ * (bm, bn) one of (256,128), (128,128), (256,64), (128,64) with M % bm == 0 and N % bn == 0, RIH_EINVAL otherwise; its statistics
+ * blocks are bm / 4 rows high.  rih_rows(d) == rih_rows_tiled(d, the tile of rih_rows_tile(d)): same instantiation, same grid.
+ * Nothing on the product path names a tile; the tests do, to reach every instantiation at shapes of a few workgroups. */
 /* The stem convolution (ABI 18): 7 x 7 / stride 2 / padding 3 over a FOUR-channel NHWC image batch (encoder.resnet.conv1 of
  * torchvision ResNet-50 via models/encoder.py:107-116, on the 3 -> 4 channel padded input of rih_nchw_to_nhwc) on the rows kernel with
  * an im2col loader (one tap of one output pixel = one float4).  Descriptor = rih_conv3_desc: x [imgs][H][W][4] (C = ldx = 4), w_h2 =
@@ -289,6 +295,8 @@ int rih_stem(const rih_conv3_desc* d, void* stream);
 int rih_rows_ok(const rih_panel_desc* d);
 int rih_rows_stats_rows(const rih_panel_desc* d);
 int rih_rows(const rih_panel_desc* d, void* stream);
+int rih_rows_tile(const rih_panel_desc* d, int* bm, int* bn);
+int rih_rows_tiled(const rih_panel_desc* d, int bm, int bn, void* stream);
 
 /* Finish a forward split-K GEMM: C[m*ldc+n] = act(alpha * sum_s P[s][m][n] + bias[n] + R[m*ldr+n]). */
 int rih_splitk_finish(const float* P, int S, int M, int N, float* C, int ldc, const float* bias, const float* R,
@@ -665,7 +673,7 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc, opt state, adam dev entry (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 25
+#define RIH_ABI_VERSION 26
 #define RIH_ABI_NSIZES 14
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);

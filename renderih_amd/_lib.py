@@ -144,6 +144,8 @@ SIGNATURES = {
     'rih_rows_ok': (c_i, [C.POINTER(PanelDesc)]),
     'rih_rows_stats_rows': (c_i, [C.POINTER(PanelDesc)]),
     'rih_rows': (c_i, [C.POINTER(PanelDesc), C.c_void_p]),
+    'rih_rows_tile': (c_i, [C.POINTER(PanelDesc), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'rih_rows_tiled': (c_i, [C.POINTER(PanelDesc), c_i, c_i, C.c_void_p]),
     'rih_hardswish_fwd': (c_i, [c_f, c_f, c_l, C.c_void_p]),
     'rih_hardswish_bwd': (c_i, [c_f, c_f, c_f, c_l, C.c_void_p]),
     'rih_tanh_scale_fwd': (c_i, [c_f, c_f, c_l, c_fl, C.c_void_p]),
@@ -251,7 +253,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 25     # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 26     # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 

@@ -758,9 +758,10 @@ void panel_launch(const PanelArgs& a, unsigned grid, bool stats, bool res, hipSt
 // k-tile in flight.  Here the recipe of conv3x3_halo_kernel is applied to plain rows: 512 threads, a BM x BN tile of 256 x 128
 // (128 x 128, 256 x 64, 128 x 64 for problems that would not fill the chip otherwise), the weights as pre-split H2 planes staged
 // global -> LDS by LDS-DMA (no conversion, no VGPR round trip for B), the A rows global -> registers -> converted ONCE per tile ->
-// LDS, THREE A stages and two B stages so that the loads of k-tile t + 2 are issued at the top of k-tile t and stored at its
-// end: every request has a whole k-tile of MFMAs to land, one barrier per k-tile, and nothing is in flight across a barrier
-// except what that barrier publishes.  Arithmetic: engine 2, product for product (see conv3x3_halo_kernel); k-order identical to
+// LDS.  TWO A stages in LDS plus two register sets of A rows in flight, THREE W stages: the requests of k-tile t + 2 (A rows into
+// registers, weights by LDS-DMA into the stage read in iteration t - 1) are issued at the top of k-tile t, and the rows of k-tile
+// t + 1 are converted into the other A stage at its end, behind a FULL wait (vmcnt(0), see the schedule below: a counted wait is
+// wrong on this part) -- one barrier per k-tile.  Arithmetic: engine 2, product for product (see conv3x3_halo_kernel); k-order identical to
 // the tiled kernel's (k ascending in 32-deep tiles), so the two agree to the last bit wherever their accumulation order inside a
 // tile agrees, and to fp32 round-off in general.
 // LDS images: a row (of A or of W) is 8 units of 16 bytes, unit j = (k / 8) * 2 + plane at position j ^ ((row >> 1) & 7) -- the
@@ -863,10 +864,10 @@ __global__ __launch_bounds__(NT, 2) void rows_kernel(const RowsArgs p) {
 
     float4 areg[2][NPA];                                // two k-tiles of A rows in flight / landed (indexed by literal parity below)
     // Every request of the main loop -- the A rows (buffer loads) and the weights (LDS-DMA) -- is issued through inline assembly,
-    // OUTSIDE hipcc's wait-count bookkeeping, and waited for with counted waits: the compiler's own placement drains vmcnt to 0 in
-    // front of every barrier behind an LDS-DMA and in front of every conversion behind a conditional request, which leaves each
-    // request ONE k-tile of MFMAs to land -- and a round trip to L2 / HBM on this part (0.7-2 us under load) is longer than a
-    // k-tile (0.5-1 us).  Requests past the last k-tile are issued all the same (out-of-range offset: zeros, no memory access; the
+    // OUTSIDE hipcc's wait-count bookkeeping, and waited for by ONE explicit vmcnt(0) per k-tile, behind the MFMAs (the compiler's
+    // own placement drains vmcnt to 0 in front of every barrier behind an LDS-DMA and in front of every conversion behind a
+    // conditional request, i.e. in front of the MFMAs).  The waits were designed as counted ones and are not: see the schedule
+    // below.  Requests past the last k-tile are issued all the same (out-of-range offset: zeros, no memory access; the
     // weights of the last k-tile again into a free stage), so that the number of requests per iteration is a compile-time constant.
     const c3_i32x4 rsA = {(int)(unsigned)(uintptr_t)p.a, (int)((unsigned long long)(uintptr_t)p.a >> 32), (int)0x7fffffff, (int)0x00020000};
 #define RIH_RW_LOAD_A(SET_, KT_)                        /* global -> registers: columns [32 KT_, 32 KT_ + 32) of the tile's rows */ \
@@ -1242,15 +1243,23 @@ extern "C" int rih_rows_stats_rows(const rih_panel_desc* d) {
     return bm / 4;
 }
 
-extern "C" int rih_rows(const rih_panel_desc* d, void* stream) {
+/* the tile rih_rows takes for this descriptor; 0 (outputs untouched): not a shape of the kernel */
+extern "C" int rih_rows_tile(const rih_panel_desc* d, int* bm, int* bn) {
+    if (!bm || !bn || !rows_ok(d) || (d->stats && d->r)) return 0;
+    rows_tile(d, *bm, *bn);
+    return 1;
+}
+
+/* rih_rows' launch on a tile the caller names (the tests reach every instantiation at one-workgroup shapes through this; the
+ * statistics blocks are bm / 4 rows high) */
+extern "C" int rih_rows_tiled(const rih_panel_desc* d, int bm, int bn, void* stream) {
     if (!rows_ok(d) || (d->stats && d->r)) return RIH_EINVAL;
+    if (!((bm == 256 || bm == 128) && (bn == 128 || bn == 64)) || d->M % bm != 0 || d->N % bn != 0) return RIH_EINVAL;
     RowsArgs a;
     a.a = d->a; a.w = (const unsigned char*)d->w_h2; a.c = d->c; a.r = d->r; a.stats = d->stats;
     a.amax_a = d->amax_a; a.amax_w = d->amax_w;
     a.M = d->M; a.N = d->N; a.K = d->K; a.lda = d->lda; a.ldc = d->ldc; a.ldr = d->ldr; a.relu = d->relu ? 1 : 0;
     a.H = a.W = a.Ho = a.Wo = 0;
-    int bm, bn;
-    rows_tile(d, bm, bn);
     a.nblk = d->N / bn;
     a.mtiles = d->M / bm;
     const unsigned grid = (unsigned)((long long)a.mtiles * a.nblk);
@@ -1261,6 +1270,13 @@ extern "C" int rih_rows(const rih_panel_desc* d, void* stream) {
     else if (bm == 256) rows_launch<256, 64>(a, grid, st, rs, s);
     else rows_launch<128, 64>(a, grid, st, rs, s);
     return (int)hipGetLastError();
+}
+
+extern "C" int rih_rows(const rih_panel_desc* d, void* stream) {
+    if (!rows_ok(d) || (d->stats && d->r)) return RIH_EINVAL;
+    int bm, bn;
+    rows_tile(d, bm, bn);       // (always a tile that divides M and N)
+    return rih_rows_tiled(d, bm, bn, stream);
 }
 
 extern "C" int rih_stem_ok(const rih_conv3_desc* d) { return stem_ok(d) ? 1 : 0; }

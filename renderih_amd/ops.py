@@ -857,13 +857,14 @@ def _halo3_ok(x, Cch, Nout, KH, KW, stride, pad, bias=None, residual=None):
             and x.is_contiguous() and x.data_ptr() % 16 == 0 and 4 * H * W_ * Cx < (1 << 31))
 
 
-def _e2_launch(entry, d, act, w, Cx, for_dgrad, Kp, bact, bw, stats, flops, tag, stats_rows=None):
+def _e2_launch(entry, d, act, w, Cx, for_dgrad, Kp, bact, bw, stats, flops, tag, stats_rows=None, call=None):
     """The launch sequence the engine-2 kernels of csrc/rih_conv3.hip share.  entry: 'rih_conv3x3' / 'rih_panel' / 'rih_rows' /
     'rih_stem' -- the library's <entry>_ok, <entry>_stats_rows and <entry> are used.  d: the entry's descriptor, filled but for
     w_h2, the two bounds and stats.  act: the activation operand; bact / bw: bounds (blocks or thunks) of it and of the OIHW weight
     w, whose H2 operand is _h2_weight(w, Cx, for_dgrad) with a reduction of Kp.  stats: a StatsHolder to fill, or None; its block
-    height is `stats_rows` or the library's answer.  tag: the PROFILE 9-tuple, (output rows, output columns, ...).  Returns False,
-    with nothing enqueued and no bound resolved, when the library refuses the descriptor: the caller takes rih_gemm."""
+    height is `stats_rows` or the library's answer.  tag: the PROFILE 9-tuple, (output rows, output columns, ...).  call: the launch
+    itself, (library, descriptor reference, stream) -> code, where it is not <entry>(descriptor, stream).  Returns False, with
+    nothing enqueued and no bound resolved, when the library refuses the descriptor: the caller takes rih_gemm."""
     lib = _L()
     amax_act = 'amax_x' if hasattr(d, 'amax_x') else 'amax_a'         # (rih_conv3_desc / rih_panel_desc name it differently)
     d.w_h2 = d.amax_w = act.data_ptr()          # (placeholders for the library's own precondition check)
@@ -885,7 +886,8 @@ def _e2_launch(entry, d, act, w, Cx, for_dgrad, Kp, bact, bw, stats, flops, tag,
         stats.T = M // stats.rows
         stats.part = torch.empty((stats.T, 2, N), device=act.device, dtype=torch.float32)
         d.stats = stats.part.data_ptr()
-    _profiled(flops, tag, lambda: check(getattr(lib, entry)(C.byref(d), _stream()), entry))
+    fn = getattr(lib, entry) if call is None else (lambda dref, stream: call(lib, dref, stream))
+    _profiled(flops, tag, lambda: check(fn(C.byref(d), _stream()), entry))
     return True
 
 
@@ -926,9 +928,9 @@ def _panel_ok(a2d_rows, K, N, lda, a, bias=None):
     return (a2d_rows // (8192 // K)) * (N // bn) >= 256
 
 
-def _plain_rows_launch(entry, code, a, w, c, M, N, K, lda, ldc, for_dgrad, relu, stats, R, ldr, ba, bw):
+def _plain_rows_launch(entry, code, a, w, c, M, N, K, lda, ldc, for_dgrad, relu, stats, R, ldr, ba, bw, stats_rows=None, call=None):
     """panel_gemm / rows_gemm: one descriptor (rih_panel_desc), one contract; `code` is the kernel's number in the PROFILE tag.
-    The statistics epilogue is not taken together with a residual."""
+    The statistics epilogue is not taken together with a residual.  stats_rows / call: see _e2_launch."""
     from ._lib import PanelDesc
     Cout, Cin = w.shape[0], w.shape[1]
     d = PanelDesc()
@@ -936,7 +938,7 @@ def _plain_rows_launch(entry, code, a, w, c, M, N, K, lda, ldc, for_dgrad, relu,
     d.M, d.N, d.K, d.lda, d.ldc, d.ldr, d.relu = M, N, K, lda, ldc, ldr, 1 if relu else 0
     assert (N, K) == ((Cin, Cout) if for_dgrad else (Cout, Cin))
     return _e2_launch(entry, d, a, w, Cin, for_dgrad, K, ba, bw, stats if R is None else None,
-                      2.0 * M * N * K, (M, N, K, 1, 0, 3, code, 1, 2))
+                      2.0 * M * N * K, (M, N, K, 1, 0, 3, code, 1, 2), stats_rows=stats_rows, call=call)
 
 
 def panel_gemm(a, w, c, M, N, K, lda, ldc, for_dgrad, relu=False, stats=None, R=None, ldr=0, ba=None, bw=None):
@@ -978,11 +980,17 @@ def _rows_ok(a2d_rows, K, N, lda, a, bias=None, c=None, R=None):
     return (a2d_rows // 128) * (N // 64) >= ROWS_MIN_WGS
 
 
-def rows_gemm(a, w, c, M, N, K, lda, ldc, for_dgrad, relu=False, stats=None, R=None, ldr=0, ba=None, bw=None):
+def rows_gemm(a, w, c, M, N, K, lda, ldc, for_dgrad, relu=False, stats=None, R=None, ldr=0, ba=None, bw=None, tile=None):
     """Enqueue rih_rows: c[M][N] = act(a[M][K] W^T (+ R)) with W = the OIHW 1x1 weight `w` as forward (n = co, k = ci) or
     data-gradient (n = ci, k = co) H2 operand.  stats: a StatsHolder, filled.  ba / bw: bound thunks of a and w.  Returns False
-    (nothing enqueued) when the library refuses the descriptor: the caller then takes rih_gemm."""
-    return _plain_rows_launch('rih_rows', 52, a, w, c, M, N, K, lda, ldc, for_dgrad, relu, stats, R, ldr, ba, bw)
+    (nothing enqueued) when the library refuses the descriptor: the caller then takes rih_gemm.  tile = (bm, bn): the same launch
+    on that tile instead of the library's choice (rih_rows_tiled; statistics blocks of bm / 4 rows) -- for the tests, which reach
+    every instantiation of the kernel at small shapes this way; a tile the library refuses raises."""
+    if tile is None:
+        return _plain_rows_launch('rih_rows', 52, a, w, c, M, N, K, lda, ldc, for_dgrad, relu, stats, R, ldr, ba, bw)
+    bm, bn = int(tile[0]), int(tile[1])
+    return _plain_rows_launch('rih_rows', 52, a, w, c, M, N, K, lda, ldc, for_dgrad, relu, stats, R, ldr, ba, bw, stats_rows=bm // 4,
+                              call=lambda lib, dref, stream: lib.rih_rows_tiled(dref, bm, bn, stream))
 
 
 # --------------------------------------------------------------------------------------------- stem convolution

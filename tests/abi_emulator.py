@@ -515,6 +515,19 @@ class EmulatedLib:
             return -1
         return self._panel_like(d, self.rih_rows_stats_rows)
 
+    def rih_rows_tile(self, dref, bm, bn):
+        d = dref._obj if hasattr(dref, '_obj') else dref
+        if not self._rows_ok(d):
+            return 0
+        (bm._obj if hasattr(bm, '_obj') else bm).value, (bn._obj if hasattr(bn, '_obj') else bn).value = self._rows_tile(d)
+        return 1
+
+    def rih_rows_tiled(self, dref, bm, bn, stream):
+        d = dref._obj if hasattr(dref, '_obj') else dref
+        if not self._rows_ok(d) or (bm, bn) not in ((256, 128), (128, 128), (256, 64), (128, 64)) or d.M % bm or d.N % bn:
+            return -1
+        return self._panel_like(d, lambda _d: bm // 4)
+
     def _panel_like(self, d, stats_rows):
         sw = self._e2_scale(d.amax_w)
         pl = np.ctypeslib.as_array((C.c_uint16 * (2 * d.N * d.K)).from_address(int(d.w_h2))).reshape(d.N, d.K // 8, 2, 8)

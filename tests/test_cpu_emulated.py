@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import test_gpu_ops as G
+import test_gpu_rows_tiles as TRT
 from abi_emulator import emulated_abi
 from renderih_amd import assets, testing
 from renderih_amd.testing import assert_close
@@ -14,6 +15,7 @@ from renderih_amd.testing import assert_close
 @pytest.fixture(autouse=True)
 def _emulate(monkeypatch):
     monkeypatch.setattr(G, 'dev', lambda: torch.device('cpu'))
+    monkeypatch.setattr(TRT, 'dev', lambda: torch.device('cpu'))
     with emulated_abi():
         yield
 
@@ -162,6 +164,19 @@ def test_rows_host_logic(monkeypatch):
     G.test_rows_1x1((1, 16, 8, 96, 128, True, True))
     G.test_rows_kernel_is_taken_and_falls_back(monkeypatch)
     G.test_stem_conv((2, 32, 32, True, True))
+
+
+def test_rows_tiled_host_logic():
+    """ops.rows_gemm(tile=...) on the emulated ABI: the route to rih_rows_tiled, statistics blocks of bm / 4 rows for a named tile,
+    pitched operands, the data-gradient weight form, the refusals of rih_rows_tiled / rih_rows_tile."""
+    for tile in TRT.TILES:
+        for K in (64, 96):
+            for epi in ('stats', 'res'):
+                TRT.check_rows_tile(tile, (2, 1), K, epi)
+        TRT.check_rows_tile(tile, (1, 1), 96, 'stats_relu')
+        TRT.check_rows_tile(tile, (2, 1), 96, 'res', for_dgrad=True)
+        TRT.check_rows_tile(tile, (2, 1), 96, 'res', pitched=True)
+    TRT.check_refusals()
 
 
 def test_conv1x1_cat_host_logic():

@@ -322,9 +322,10 @@ def test_panel_1x1(case, monkeypatch=None):
         ops.ENGINE, ops.PANEL, ops._panel_ok = saved
 
 
-# (N, H, W, Cin, Cout, relu, stats): every tile of rows_kernel -- 256 x 128 (M % 256 == 0, N % 128 == 0, >= 256 workgroups only at
-# bench sizes: the small cases below force tiles through the row / column counts), 128 x 128, 256 x 64, 128 x 64 -- K from one k-tile
-# pair to 1024, K not a multiple of 64, residual and statistics epilogues
+# (N, H, W, Cin, Cout, relu, stats): rih_rows as Conv2dFn reaches it.  With at most 768 rows rows_tile() gives these launches
+# rows_kernel<128, 64> (Cout or, for the data gradient, Cin not a multiple of 128) or <128, 128>, never a 256-row tile (those need
+# >= 256 workgroups; tests/test_gpu_rows_tiles.py names the tile instead and covers all four) -- K from one k-tile pair to 1024, K
+# not a multiple of 64, residual and statistics epilogues
 ROWS_CASES = [(2, 16, 16, 256, 64, False, True), (1, 16, 8, 96, 128, True, True), (2, 8, 8, 512, 192, False, False),
               (1, 16, 16, 1024, 64, True, True), (1, 8, 16, 64, 256, False, True), (3, 16, 8, 160, 320, True, False)]
 
@@ -335,7 +336,9 @@ def test_rows_1x1(case, monkeypatch=None):
     as 512-thread workgroups with three LDS-DMA-staged stages of H2 weight planes, two A stages in LDS and the A prefetch in registers -- forward (+ ReLU, + BatchNorm statistics), the
     data gradient WITH the skip path's gradient as residual (conv2d_skip: Bottleneck.conv1), the weight gradient (rih_gemm) --
     against fp64 (gradients at rtol 1e-4 + 1e-5 max: north_star's bar), and against the tiled kernels (ROWS off).  The planning
-    thresholds (K >= 256, N >= 128, >= 128 workgroups) are lifted for the small shapes; the panel kernel is off so that K = 64 / 128 come here."""
+    thresholds (K >= 256, N >= 128, >= 128 workgroups) are lifted for the small shapes; the panel kernel is off so that K = 64 / 128 come here.
+    The tile is the library's choice, at these sizes 128 x 64 or 128 x 128 only, and the statistics are checked after merging the
+    blocks; tests/test_gpu_rows_tiles.py has every tile and the statistics block by block."""
     from renderih_amd import ops
     N, H, W, Cin, Cout, relu, want_stats = case
     saved = (ops.ENGINE, ops.ROWS, ops.ROWS_MINK, ops.ROWS_MIN_WGS, ops.PANEL, ops.ROWS_MIN_M, ops.ROWS_MIN_N)
@@ -381,7 +384,8 @@ def test_rows_1x1(case, monkeypatch=None):
 def test_rows_and_stem_kernels_are_reproducible_at_bench_size():
     """Sixty launches of rih_rows on the HBM-bound 262144 x 256 -> 64 shapes (forward with statistics, data gradient with residual)
     and twenty of rih_stem at B = 64, every second one on an operand fresh out of a producer kernel, with unrelated traffic behind
-    each launch: all outputs bit-identical to the first.  Round 6: the kernels issue their requests through inline assembly; a
+    each launch: all outputs bit-identical to the first, and the first rih_rows output of either form (with the forward's statistics,
+    block by block) equal to an fp64 matmul on the device at the suite's bar.  Round 6: the kernels issue their requests through inline assembly; a
     COUNTED wait (vmcnt(N), N > 0) across LDS-DMA requests and buffer loads let 6 of 800 such launches convert registers whose
     load had not landed (profiles/r06/rows/c14_*), which no small-shape parity test saw -- the waits are vmcnt(0) since."""
     if dev().type != 'cuda':
@@ -401,10 +405,25 @@ def test_rows_and_stem_kernels_are_reproducible_at_bench_size():
         for rep in range(60):
             a = torch.relu(src * 1.3 + 0.2) if rep % 2 else a0
             c = torch.empty(M, N, device=d)
-            assert ops.rows_gemm(a, w, c, M, N, K, K, N, not fwd, stats=ops.StatsHolder() if fwd else None, R=R, ldr=N, ba=ba, bw=bw)
+            holder = ops.StatsHolder() if fwd else None
+            assert ops.rows_gemm(a, w, c, M, N, K, K, N, not fwd, stats=holder, R=R, ldr=N, ba=ba, bw=bw)
             scratch.normal_()
             if first is None:
                 first = c.clone()
+                # ... and the first is RIGHT: fp64 on the device from the same fp32 operands, at the bar of test_rows_1x1
+                w2 = w[:, :, 0, 0].double()
+                ref = a0.double() @ (w2.t() if fwd else w2)
+                if R is not None:
+                    ref += R.double()
+                what = 'rih_rows at bench size (%s)' % ('fwd' if fwd else 'dgrad')
+                assert_close(first, ref, 1e-4, 1e-5, what)
+                if fwd:
+                    assert holder.rows in (32, 64) and holder.T == M // holder.rows
+                    blk = ref.reshape(holder.T, holder.rows, N)
+                    mean = blk.mean(1)
+                    assert_close(holder.part[:, 0], mean, 1e-4, 1e-5, what + ' block means')
+                    assert_close(holder.part[:, 1], ((blk - mean[:, None]) ** 2).sum(1), 1e-3, 1e-5, what + ' block M2')
+                del ref
             else:
                 assert torch.equal(c, first), 'rih_rows launch %d (%s) differs from the first' % (rep, 'fwd' if fwd else 'dgrad')
     img = torch.randn(64, 256, 256, 4, device=d)

@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.join(HERE, 'hipcpu'))
 import test_gpu_loss as TL          # noqa: E402
 import test_gpu_mano as TMANO       # noqa: E402
 import test_gpu_ops as G            # noqa: E402
+import test_gpu_rows_tiles as TRT   # noqa: E402
 import test_metrics as TMET         # noqa: E402
 import test_pose_head as TP         # noqa: E402
 
@@ -26,7 +27,7 @@ CPU = torch.device('cpu')
 @pytest.fixture(autouse=True)
 def _host_kernels(monkeypatch):
     from host_kernels import host_kernels_abi
-    for mod in (G, TL, TMANO):
+    for mod in (G, TL, TMANO, TRT):
         monkeypatch.setattr(mod, 'dev', lambda: CPU)
     with host_kernels_abi():
         yield
@@ -93,9 +94,31 @@ def test_panel_kernels(case):
 @pytest.mark.parametrize('case', [(2, 16, 16, 256, 64, False, True), (1, 16, 8, 96, 128, True, True), (1, 8, 16, 64, 256, False, True),
                                   (3, 16, 8, 160, 320, True, False)])
 def test_rows_kernels(case):
-    """csrc/rih_conv3.hip rows_kernel on the host harness: LDS-DMA-staged weight planes on two stages, three A stages rotating,
-    tiles 128 x 64 / 128 x 128 / 256 x 64, one to eight k-tiles, residual and statistics epilogues."""
+    """csrc/rih_conv3.hip rows_kernel on the host harness: LDS-DMA-staged weight planes on three stages, two A stages in LDS and
+    the A prefetch in registers, two to eight k-tiles, residual and statistics epilogues -- on the tiles rih_rows picks at these
+    sizes, 128 x 64 and 128 x 128 (test_rows_tile_kernels has the 256-row ones)."""
     G.test_rows_1x1(case)
+
+
+@pytest.mark.parametrize('tile', TRT.TILES, ids=lambda t: '%dx%d' % t)
+def test_rows_tile_kernels(tile):
+    """rows_kernel<256, 128> / <128, 128> / <256, 64> / <128, 64> through rih_rows_tiled on the host harness, one and two
+    workgroups, two and three (odd) k-tiles, statistics block by block and residual, and a launch with lda > K, ldc > N, ldr > N
+    on poisoned buffers -- the checks of tests/test_gpu_rows_tiles.py.  What can show here: indexing, the LDS swizzle, the rotation
+    of the stages, the odd trip count's tail, the addressing of the epilogue (output, residual, statistics slots) on every tile.
+    What cannot: the hazards of the inline-assembly requests (a wait that lets a load land late, a dead load's registers handed
+    to a live value) -- on the host a load completes at once; only the GPU run of those tests sees them."""
+    for grid in ((1, 1), (2, 1)):
+        for K in (64, 96):
+            for epi in ('stats', 'res'):
+                TRT.check_rows_tile(tile, grid, K, epi)
+    TRT.check_rows_tile(tile, (2, 1), 96, 'stats_relu')
+    TRT.check_rows_tile(tile, (2, 1), 96, 'res', for_dgrad=True)
+    TRT.check_rows_tile(tile, (2, 1), 96, 'res', pitched=True)
+
+
+def test_rows_tiled_refusals_on_the_host_library():
+    TRT.check_refusals()
 
 
 @pytest.mark.parametrize('case', [(2, 32, 32, True, True), (4, 16, 16, True, False)])
