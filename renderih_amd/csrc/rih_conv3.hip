@@ -11,9 +11,10 @@
 // "H2", written once per step by rih_h2_conv_weight / rih_h2_multi) and are staged global -> LDS by LDS-DMA: no VGPR round
 // trip, no ds_write, no conversion for B at all.  One barrier per k-tile; B double-buffered, A double-buffered per chunk.
 //
-// Arithmetic = engine 2 of rih_gemm.hip, bit for bit per product: operands scaled by powers of two derived from device-resident
-// bound blocks (e2_scale), x = hi + 2^-11 lo with fp16 hi / lo, three v_mfma_f32_32x32x16_f16 per 32x32x16 block (hi*hi into
-// acc0, lo*hi + hi*lo into acc1), result (acc0 + 2^-11 acc1) / (s_a s_b).  The summation ORDER over k differs from the tap-major
+// Arithmetic = engine 2 (rih_e2.h: the scale, the split, the three-product MFMA step, the epilogue fold and the statistics are
+// the ones rih_gemm.hip uses), bit for bit per product: operands scaled by powers of two derived from device-resident bound
+// blocks (e2_scale), x = hi + 2^-11 lo with fp16 hi / lo, three v_mfma_f32_32x32x16_f16 per 32x32x16 block (hi*hi into acc0,
+// lo*hi + hi*lo into acc1), result (acc0 + 2^-11 acc1) / (s_a s_b).  The summation ORDER over k differs from the tap-major
 // implicit GEMM (here chunk-major: (c / 32, tap, c % 32)), so results agree to fp32 round-off, not bitwise.
 //
 // Geometry: 512 threads = 8 wavefronts; a patch is 256 pixels of one image -- 8 rows x 32 pixels (W % 32 == 0) or 16 x 16 (maps
@@ -26,25 +27,23 @@
 // 16-lane group for every tap shift (checked exhaustively by tests/test_kernels_on_cpu.py::test_conv3_lds_image_is_conflict_free).
 //
 // Preconditions (rih_conv3x3_ok): C % 32 == 0, N % 32 == 0, (H % 8 == 0 and W % 32 == 0) or (H % 16 == 0 and W % 16 == 0),
-// 16-byte aligned operands, pitches % 4 == 0, one image < 2 GiB.  Epilogue: optional ReLU, optional BatchNorm statistics per 64-row wave block ((mean, M2), the format of
-// rih_gemm_desc.stats: rih_bn_stats_from_blocks merges them), or an optional residual added before the ReLU (RES variants, ABI 19:
-// the skip gradient in the data gradient of a BasicBlock's first convolution).  No bias (no 3x3 convolution of the network has one
-// on the training path); callers with one use rih_gemm.
+// 16-byte aligned operands, pitches % 4 == 0, one image < 2 GiB.  Epilogue: optional ReLU, optional BatchNorm statistics per
+// 64-row wave block ((mean, M2), the format of rih_gemm_desc.stats: rih_bn_stats_from_blocks merges them), or an optional
+// residual added before the ReLU (RES variants, ABI 19: the skip gradient in the data gradient of a BasicBlock's first
+// convolution).  No bias (no 3x3 convolution of the network has one on the training path); callers with one use rih_gemm.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include "../../include/renderih_amd.h"
+#include "rih_e2.h"
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
 constexpr int A_STAGE = 340 * 128;                                       // bytes: the larger halo (10 x 34), 8 units of 16 B per pixel
 constexpr int NT = 512;
-constexpr unsigned OOB = 0x80000000u;
-constexpr int SLD = 36;                                                  // epilogue staging pitch (floats)
 
 struct C3Args {
     const float* x;
@@ -58,68 +57,6 @@ struct C3Args {
     const float* r;             // RES: residual [imgs][H][W][ldr], added before the ReLU (the skip gradient of a BasicBlock's first conv)
     int ldr;
 };
-
-__device__ __forceinline__ int xcd_remap_c3(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + (bid >> 3);
-}
-
-// the same scale derivation as rih_gemm.hip's e2_scale (bound block: 64 partial maxima, one per 128-byte line)
-__device__ __forceinline__ float c3_scale(const float* amax) {
-    if (amax == nullptr) return 1.f;
-    float a = amax[(threadIdx.x & 63) * (RIH_BOUND_FLOATS / 64)];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
-    a = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(a)));
-    const int e = (int)((__float_as_uint(a) >> 23) & 0xffu);
-    if (e == 0 || e == 255) return 1.f;
-    int se = 268 - e;
-    se = se > 253 ? 253 : se;
-    return __uint_as_float((unsigned)se << 23);
-}
-
-__device__ __forceinline__ unsigned c3_pk_f16(float a, float b) {
-    const f16x2 v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
-// (a, b) * s -> packed fp16 hi pair and packed fp16 pair of the 2^11-scaled residuals (rih_gemm.hip split2h)
-__device__ __forceinline__ void c3_split2h(float a, float b, float s, unsigned& h, unsigned& l) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    float ra, rb;
-    const float k2048 = 2048.f;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(a), "s"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(b), "s"(s));
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(ra) : "v"(a), "s"(s), "v"(h));
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(rb) : "v"(b), "s"(s), "v"(h));
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(l) : "v"(ra), "s"(k2048));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(l) : "v"(rb), "s"(k2048));
-#else
-    a *= s;
-    b *= s;
-    const f16x2 hv = {(_Float16)a, (_Float16)b};
-    h = __builtin_bit_cast(unsigned, hv);
-    l = c3_pk_f16((a - (float)hv.x) * 2048.f, (b - (float)hv.y) * 2048.f);
-#endif
-}
-
-// c3_split2h pinned in program order (volatile): rows_kernel converts the rows of k-tile j + 1 BEHIND its counted wait -- hoisted
-// into the MFMA phase (where the scheduler likes to put it) the conversion needs those rows at the top of the iteration and the
-// prefetch is one k-tile deep again
-__device__ __forceinline__ void c3_split2h_pinned(float a, float b, float s, unsigned& h, unsigned& l) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    float ra, rb;
-    const float k2048 = 2048.f;
-    asm volatile("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(a), "s"(s));
-    asm volatile("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(b), "s"(s));
-    asm volatile("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(ra) : "v"(a), "s"(s), "v"(h));
-    asm volatile("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(rb) : "v"(b), "s"(s), "v"(h));
-    asm volatile("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(l) : "v"(ra), "s"(k2048));
-    asm volatile("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(l) : "v"(rb), "s"(k2048));
-#else
-    c3_split2h(a, b, s, h, l);
-#endif
-}
 
 __device__ __forceinline__ void c3_glds16(const unsigned char* src, unsigned char* lds_dst) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
@@ -159,12 +96,6 @@ __device__ __forceinline__ void c3_vm_wait() {
 #endif
 }
 
-__device__ __forceinline__ float4 c3_bload4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-
 // A 16-byte buffer load outside hipcc's wait-count bookkeeping, like c3_glds16_raw: the destination registers are the kernel's to
 // wait for (c3_vm_wait) before their first use.  `rs` = the four words of a raw buffer resource (base, base_hi, num_records, flags);
 // an offset beyond num_records returns zeros (the hardware range check, as with the builtin).
@@ -176,7 +107,7 @@ __device__ __forceinline__ float4 c3_bload4_raw(c3_i32x4 rs, __amdgpu_buffer_rsr
     asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "=v"(v) : "v"(off), "s"(rs) : "memory");
     return make_float4(v.x, v.y, v.z, v.w);
 #else
-    return c3_bload4(r, off);
+    return bload4(r, off);
 #endif
 }
 
@@ -201,7 +132,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_kernel(const C3Args p) {
     const int wm = wave / WGN, wn = wave % WGN;
 
     // workgroup -> (image, patch, channel block); channel blocks fastest so that workgroups sharing a halo are neighbours
-    const int bid = xcd_remap_c3((int)blockIdx.x, (int)gridDim.x);
+    const int bid = xcd_remap((int)blockIdx.x, (int)gridDim.x);
     const int nb = bid % p.nblk;
     int rest = bid / p.nblk;
     const int tx_t = rest % p.tiles_x;
@@ -212,7 +143,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_kernel(const C3Args p) {
     // 32-row MFMA block blk (0..7) of the patch, lane l31 -> pixel (ty, tx): one image row of 32, or two rows of 16
     const int lty = (TW == 32) ? 0 : (l31 >> 4), ltx = l31 & (TW - 1);
 
-    const float sa = c3_scale(p.amax_x), sb = c3_scale(p.amax_w);
+    const float sa = e2_scale(p.amax_x), sb = e2_scale(p.amax_w);
 
     const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(p.x + (long long)img * p.H * p.W * p.ldx), (short)0, (int)((long long)p.H * p.W * p.ldx * 4), 0x00020000);
@@ -262,15 +193,15 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_kernel(const C3Args p) {
     auto load_A = [&](int c0) {                         // global -> registers: the halo of channels [c0, c0 + 32)
         const unsigned add = (unsigned)c0 * 4u;
 #pragma unroll
-        for (int i = 0; i < NPA; ++i) areg[i] = c3_bload4(rX, a_goff[i] == OOB ? OOB : a_goff[i] + add);
+        for (int i = 0; i < NPA; ++i) areg[i] = bload4(rX, a_goff[i] == OOB ? OOB : a_goff[i] + add);
     };
     auto store_A = [&](unsigned char* dst) {            // registers -> two fp16 planes in LDS
 #pragma unroll
         for (int i = 0; i < NPA; ++i) {
             if (a_lds[i] < 0) continue;
             unsigned h0, l0, h1, l1;
-            c3_split2h(areg[i].x, areg[i].y, sa, h0, l0);
-            c3_split2h(areg[i].z, areg[i].w, sa, h1, l1);
+            e2_split2h(areg[i].x, areg[i].y, sa, h0, l0);
+            e2_split2h(areg[i].z, areg[i].w, sa, h1, l1);
             *reinterpret_cast<uint2*>(dst + a_lds[i]) = make_uint2(h0, h1);
             *reinterpret_cast<uint2*>(dst + (a_lds[i] ^ 16)) = make_uint2(l0, l1);
         }
@@ -329,13 +260,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_kernel(const C3Args p) {
 #pragma unroll
                     for (int jj = 0; jj < TN; ++jj)
                         bv[pl][jj] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(Bs + b_rd[s][pl][jj]));
-#define RIH_C3_TERM(ACC_, PA_, PB_)                                                                               \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int jj = 0; jj < TN; ++jj) ACC_[i][jj] = \
-        __builtin_amdgcn_mfma_f32_32x32x16_f16(av[PA_][i], bv[PB_][jj], ACC_[i][jj], 0, 0, 0);
-                RIH_C3_TERM(acc1, 1, 0)
-                RIH_C3_TERM(acc, 0, 0)
-                RIH_C3_TERM(acc1, 0, 1)
-#undef RIH_C3_TERM
+                RIH_E2_MMA3(TM, TN, av, bv, acc, acc1)
             }
             if (t == 8 && c + 1 < nchunk) store_A(Abuf + ((c + 1) & 1) * A_STAGE);   // (that stage was last read in chunk c - 1)
             c3_dma_wait();                              // the weights of k-tile kt + 1 have landed before the barrier publishes them
@@ -346,15 +271,8 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_kernel(const C3Args p) {
     // ---------------------------------------------------------------- epilogue (the loop ended with a barrier: LDS is free)
     // accumulators -> this wave's 32 x SLD floats of LDS -> each lane owns 4 consecutive columns of a row: 16-byte stores
     float* stg = reinterpret_cast<float*>(smem) + wave * (32 * SLD);
-    const float inv_a = 1.f / sa, inv_b = 1.f / sb;     // (applied one after the other, like rih_gemm: exact powers of two)
-    float4 ssh[STATS ? TN : 1], ssum[STATS ? TN : 1], ssq[STATS ? TN : 1];
-    float scnt[STATS ? TN : 1];
-    if (STATS) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            ssh[j] = make_float4(0, 0, 0, 0); ssum[j] = make_float4(0, 0, 0, 0); ssq[j] = make_float4(0, 0, 0, 0); scnt[j] = 0.f;
-        }
-    }
+    const float inv_a = 1.f / sa, inv_b = 1.f / sb;     // (exact powers of two)
+    RIH_E2_STATS_DECL(STATS, TN)
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
         const int blk = wm * TM + i;                    // 32-row block of the patch: image row blk (TW 32) or rows 2 blk, 2 blk + 1
@@ -363,11 +281,7 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_kernel(const C3Args p) {
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             if (i + j > 0) __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float v = fmaf(acc1[i][j][r], 0x1p-11f, acc[i][j][r]) * inv_a * inv_b;
-                stg[((r & 3) + 8 * (r >> 2) + 4 * lhi) * SLD + l31] = v;
-            }
+            RIH_E2_STAGE(stg, SLD, acc[i][j], acc1[i][j], inv_a, inv_b, l31, lhi)
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -380,45 +294,16 @@ __global__ __launch_bounds__(NT, 2) void conv3x3_halo_kernel(const C3Args p) {
                 }
                 if (p.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                 *reinterpret_cast<float4*>(ypatch + ((long long)ty * p.W + tx) * p.ldy + j * 32 + c4) = v;
-                if (STATS) {
-                    if (scnt[j] == 0.f) ssh[j] = v;
-                    scnt[j] += 1.f;
-                    const float dx = v.x - ssh[j].x, dy = v.y - ssh[j].y, dz = v.z - ssh[j].z, dw = v.w - ssh[j].w;
-                    ssum[j].x += dx; ssum[j].y += dy; ssum[j].z += dz; ssum[j].w += dw;
-                    ssq[j].x += dx * dx; ssq[j].y += dy * dy; ssq[j].z += dz * dz; ssq[j].w += dw * dw;
-                }
+                if (STATS) RIH_E2_STATS_ADD(j, v)
             }
         }
     }
     if (STATS) {
-        // per column: (mean, centred sum of squares) of this wave's 32 TM rows; a lane holds 4 TM rows, the eight row-lanes merge
-        // pairwise with Chan's formula (store_tiles_wide of rih_gemm.hip); row block index = WGM * patch + wm
+        // statistics block of this wave's 32 TM rows: row block index = WGM * patch + wm
         const long long rb = (((long long)img * p.tiles_y + ty_t) * p.tiles_x + tx_t) * WGM + wm;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            float n = scnt[j];
-            const float in = n > 0.f ? 1.f / n : 0.f;
-            float4 mean = make_float4(ssh[j].x + ssum[j].x * in, ssh[j].y + ssum[j].y * in, ssh[j].z + ssum[j].z * in,
-                                      ssh[j].w + ssum[j].w * in);
-            float4 m2 = make_float4(ssq[j].x - ssum[j].x * ssum[j].x * in, ssq[j].y - ssum[j].y * ssum[j].y * in,
-                                    ssq[j].z - ssum[j].z * ssum[j].z * in, ssq[j].w - ssum[j].w * ssum[j].w * in);
-#pragma unroll
-            for (int o = 8; o < 64; o <<= 1) {
-                const float nbr = __shfl_xor(n, o, 64);
-                const float nt = n + nbr;
-                const float wb = nt > 0.f ? nbr / nt : 0.f;
-                const float cf = n * wb;
-#define RIH_C3_MERGE(c_)                                                              \
-    {                                                                                 \
-        const float mb = __shfl_xor(mean.c_, o, 64), qb = __shfl_xor(m2.c_, o, 64);   \
-        const float dl = mb - mean.c_;                                                \
-        mean.c_ += dl * wb;                                                           \
-        m2.c_ += qb + dl * dl * cf;                                                   \
-    }
-                RIH_C3_MERGE(x) RIH_C3_MERGE(y) RIH_C3_MERGE(z) RIH_C3_MERGE(w)
-#undef RIH_C3_MERGE
-                n = nt;
-            }
+            RIH_E2_STATS_MERGE(j, mean, m2)
             if ((lane >> 3) == 0) {
                 const int nn = n0 + wn * (BN / WGN) + j * 32 + (lane & 7) * 4;
                 *reinterpret_cast<float4*>(p.stats + (rb * 2 + 0) * p.N + nn) = mean;
@@ -454,14 +339,14 @@ __device__ __forceinline__ float h2w_fetch(const H2WArgs& a, int n, int k) {
 __device__ __forceinline__ void h2w_span(const H2WArgs& a, long long first, long long stride) {
     const int G = a.Kp / 8;
     const long long total = (long long)a.N * G;
-    const float sc = c3_scale(a.amax);
+    const float sc = e2_scale(a.amax);
     for (long long i = first; i < total; i += stride) {
         const int n = (int)(i / G), g = (int)(i - (long long)n * G);
         uint4 h, l;
-        c3_split2h(h2w_fetch(a, n, 8 * g + 0), h2w_fetch(a, n, 8 * g + 1), sc, h.x, l.x);
-        c3_split2h(h2w_fetch(a, n, 8 * g + 2), h2w_fetch(a, n, 8 * g + 3), sc, h.y, l.y);
-        c3_split2h(h2w_fetch(a, n, 8 * g + 4), h2w_fetch(a, n, 8 * g + 5), sc, h.z, l.z);
-        c3_split2h(h2w_fetch(a, n, 8 * g + 6), h2w_fetch(a, n, 8 * g + 7), sc, h.w, l.w);
+        e2_split2h(h2w_fetch(a, n, 8 * g + 0), h2w_fetch(a, n, 8 * g + 1), sc, h.x, l.x);
+        e2_split2h(h2w_fetch(a, n, 8 * g + 2), h2w_fetch(a, n, 8 * g + 3), sc, h.y, l.y);
+        e2_split2h(h2w_fetch(a, n, 8 * g + 4), h2w_fetch(a, n, 8 * g + 5), sc, h.z, l.z);
+        e2_split2h(h2w_fetch(a, n, 8 * g + 6), h2w_fetch(a, n, 8 * g + 7), sc, h.w, l.w);
         uint4* d = reinterpret_cast<uint4*>(a.dst + i * 32);
         d[0] = h;
         d[1] = l;
@@ -544,13 +429,13 @@ __global__ __launch_bounds__(NT, 2) void panel_kernel(const PanelArgs p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lhi = lane >> 5;
     const int wm = wave / WGN, wn = wave % WGN;
     const int G = (int)gridDim.x;
-    const int id = xcd_remap_c3((int)blockIdx.x, G);   // neighbours on one XCD share the row tiles (their column blocks differ)
+    const int id = xcd_remap((int)blockIdx.x, G);   // neighbours on one XCD share the row tiles (their column blocks differ)
     const int nb = id % p.nblk, n0 = nb * BN;
     const int mstep = G / p.nblk;
     int mt = id / p.nblk;
     if (mt >= p.mtiles) return;                         // (whole workgroup: before any barrier)
 
-    const float sa = c3_scale(p.amax_a), sb = c3_scale(p.amax_w);
+    const float sa = e2_scale(p.amax_a), sb = e2_scale(p.amax_w);
     const float inv_a = 1.f / sa, inv_b = 1.f / sb;
 
     // weights: LDS unit U = (row n, position pos) holds source unit j = (pos & ~15) | ((pos & 15) ^ (n & 15)); staged once
@@ -579,15 +464,15 @@ __global__ __launch_bounds__(NT, 2) void panel_kernel(const PanelArgs p) {
 #pragma unroll
         for (int i = 0; i < NPA; ++i) {
             const long long off = ((long long)tile * BM + a_row[i]) * p.lda * 4 + a_col[i];
-            areg[i] = c3_bload4(rA, (tile < p.mtiles && off < 0x7fffffffLL) ? (unsigned)off : OOB);
+            areg[i] = bload4(rA, (tile < p.mtiles && off < 0x7fffffffLL) ? (unsigned)off : OOB);
         }
     };
     auto store_A = [&](unsigned char* dst) {
 #pragma unroll
         for (int i = 0; i < NPA; ++i) {
             unsigned h0, l0, h1, l1;
-            c3_split2h(areg[i].x, areg[i].y, sa, h0, l0);
-            c3_split2h(areg[i].z, areg[i].w, sa, h1, l1);
+            e2_split2h(areg[i].x, areg[i].y, sa, h0, l0);
+            e2_split2h(areg[i].z, areg[i].w, sa, h1, l1);
             *reinterpret_cast<uint2*>(dst + a_lds[i]) = make_uint2(h0, h1);
             *reinterpret_cast<uint2*>(dst + (a_lds[i] ^ 16)) = make_uint2(l0, l1);
         }
@@ -634,26 +519,13 @@ __global__ __launch_bounds__(NT, 2) void panel_kernel(const PanelArgs p) {
                                                                    Bs + n * ROWB + (((j & ~15) | ((j & 15) ^ (n & 15))) << 4)));
                     }
                 }
-#define RIH_PN_TERM(ACC_, PA_, PB_)                                                                               \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int jj = 0; jj < TN; ++jj) ACC_[i][jj] = \
-        __builtin_amdgcn_mfma_f32_32x32x16_f16(av[PA_][i], bv[PB_][jj], ACC_[i][jj], 0, 0, 0);
-                RIH_PN_TERM(acc1, 1, 0)
-                RIH_PN_TERM(acc, 0, 0)
-                RIH_PN_TERM(acc1, 0, 1)
-#undef RIH_PN_TERM
+                RIH_E2_MMA3(TM, TN, av, bv, acc, acc1)
             }
         __syncthreads();                                // stage st is consumed by every wave; stage st ^ 1 is complete
         // ---- epilogue through this wave's 32 x 32 floats of the consumed stage
         float* stg = reinterpret_cast<float*>(Abuf + st * A_ST) + wave * (32 * 32);
         const int mbase = mt * BM + wm * (32 * TM), nbase = n0 + wn * (32 * TN);
-        float4 ssh[STATS ? TN : 1], ssum[STATS ? TN : 1], ssq[STATS ? TN : 1];
-        float scnt[STATS ? TN : 1];
-        if (STATS) {
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                ssh[j] = make_float4(0, 0, 0, 0); ssum[j] = make_float4(0, 0, 0, 0); ssq[j] = make_float4(0, 0, 0, 0); scnt[j] = 0.f;
-            }
-        }
+        RIH_E2_STATS_DECL(STATS, TN)
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -666,9 +538,7 @@ __global__ __launch_bounds__(NT, 2) void panel_kernel(const PanelArgs p) {
                                                                  j * 32 + (lane & 7) * 4);
                 }
                 if (i + j > 0) __builtin_amdgcn_wave_barrier();
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    stg[((r & 3) + 8 * (r >> 2) + 4 * lhi) * 32 + l31] = fmaf(acc1[i][j][r], 0x1p-11f, acc[i][j][r]) * inv_a * inv_b;
+                RIH_E2_STAGE(stg, 32, acc[i][j], acc1[i][j], inv_a, inv_b, l31, lhi)
                 __builtin_amdgcn_wave_barrier();
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -677,13 +547,7 @@ __global__ __launch_bounds__(NT, 2) void panel_kernel(const PanelArgs p) {
                     if (RES) { v.x += rv[q].x; v.y += rv[q].y; v.z += rv[q].z; v.w += rv[q].w; }
                     if (p.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                     *reinterpret_cast<float4*>(p.c + (long long)(mbase + i * 32 + row) * p.ldc + nbase + j * 32 + c4) = v;
-                    if (STATS) {
-                        if (scnt[j] == 0.f) ssh[j] = v;
-                        scnt[j] += 1.f;
-                        const float dx = v.x - ssh[j].x, dy = v.y - ssh[j].y, dz = v.z - ssh[j].z, dw = v.w - ssh[j].w;
-                        ssum[j].x += dx; ssum[j].y += dy; ssum[j].z += dz; ssum[j].w += dw;
-                        ssq[j].x += dx * dx; ssq[j].y += dy * dy; ssq[j].z += dz * dz; ssq[j].w += dw * dw;
-                    }
+                    if (STATS) RIH_E2_STATS_ADD(j, v)
                 }
             }
         }
@@ -691,29 +555,7 @@ __global__ __launch_bounds__(NT, 2) void panel_kernel(const PanelArgs p) {
             const long long rblk = mbase / (32 * TM);
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                float n = scnt[j];
-                const float in = n > 0.f ? 1.f / n : 0.f;
-                float4 mean = make_float4(ssh[j].x + ssum[j].x * in, ssh[j].y + ssum[j].y * in, ssh[j].z + ssum[j].z * in,
-                                          ssh[j].w + ssum[j].w * in);
-                float4 m2 = make_float4(ssq[j].x - ssum[j].x * ssum[j].x * in, ssq[j].y - ssum[j].y * ssum[j].y * in,
-                                        ssq[j].z - ssum[j].z * ssum[j].z * in, ssq[j].w - ssum[j].w * ssum[j].w * in);
-#pragma unroll
-                for (int o = 8; o < 64; o <<= 1) {
-                    const float nbr = __shfl_xor(n, o, 64);
-                    const float nt = n + nbr;
-                    const float wb = nt > 0.f ? nbr / nt : 0.f;
-                    const float cf = n * wb;
-#define RIH_PN_MERGE(c_)                                                              \
-    {                                                                                 \
-        const float mb = __shfl_xor(mean.c_, o, 64), qb = __shfl_xor(m2.c_, o, 64);   \
-        const float dl = mb - mean.c_;                                                \
-        mean.c_ += dl * wb;                                                           \
-        m2.c_ += qb + dl * dl * cf;                                                   \
-    }
-                    RIH_PN_MERGE(x) RIH_PN_MERGE(y) RIH_PN_MERGE(z) RIH_PN_MERGE(w)
-#undef RIH_PN_MERGE
-                    n = nt;
-                }
+                RIH_E2_STATS_MERGE(j, mean, m2)
                 if ((lane >> 3) == 0) {
                     const int nn = nbase + j * 32 + (lane & 7) * 4;
                     *reinterpret_cast<float4*>(p.stats + (rblk * 2 + 0) * p.N + nn) = mean;
@@ -809,11 +651,11 @@ __global__ __launch_bounds__(NT, 2) void rows_kernel(const RowsArgs p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lhi = lane >> 5;
     const int wm = wave / WGN, wn = wave % WGN;
     // workgroup -> (row tile, column block); column blocks fastest: the workgroups that share A rows are neighbours on one XCD
-    const int id = xcd_remap_c3((int)blockIdx.x, (int)gridDim.x);
+    const int id = xcd_remap((int)blockIdx.x, (int)gridDim.x);
     const int nb = id % p.nblk, mt = id / p.nblk;
     const int m0 = mt * BM, n0 = nb * BN;
 
-    const float sa = c3_scale(p.amax_a), sb = c3_scale(p.amax_w);
+    const float sa = e2_scale(p.amax_a), sb = e2_scale(p.amax_w);
 
     const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)p.a, (short)0, (int)0x7fffffff, 0x00020000);
     // A: quad q = pass * NT + tid -> row q / 8, channel quad q % 8 of the 32-deep k-tile
@@ -895,8 +737,8 @@ __global__ __launch_bounds__(NT, 2) void rows_kernel(const RowsArgs p) {
         unsigned char* const dst_ = (DST_);                                                                                  \
         _Pragma("unroll") for (int i = 0; i < NPA; ++i) {                                                                    \
             unsigned h0, l0, h1, l1;                                                                                         \
-            c3_split2h_pinned(areg[SET_][i].x, areg[SET_][i].y, sa, h0, l0);                                                 \
-            c3_split2h_pinned(areg[SET_][i].z, areg[SET_][i].w, sa, h1, l1);                                                 \
+            e2_split2h_pinned(areg[SET_][i].x, areg[SET_][i].y, sa, h0, l0);                                                 \
+            e2_split2h_pinned(areg[SET_][i].z, areg[SET_][i].w, sa, h1, l1);                                                 \
             *reinterpret_cast<uint2*>(dst_ + a_lds[i]) = make_uint2(h0, h1);                                                 \
             *reinterpret_cast<uint2*>(dst_ + (a_lds[i] ^ 16)) = make_uint2(l0, l1);                                          \
         }                                                                                                                    \
@@ -929,13 +771,7 @@ __global__ __launch_bounds__(NT, 2) void rows_kernel(const RowsArgs p) {
                 for (int jj = 0; jj < TN; ++jj)
                     bv[pl][jj] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(Bs + b_rd[s][pl][jj]));
             }
-#define RIH_RW_TERM(ACC_, PA_, PB_)                                                                               \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int jj = 0; jj < TN; ++jj) ACC_[i][jj] = \
-        __builtin_amdgcn_mfma_f32_32x32x16_f16(av[PA_][i], bv[PB_][jj], ACC_[i][jj], 0, 0, 0);
-            RIH_RW_TERM(acc1, 1, 0)
-            RIH_RW_TERM(acc, 0, 0)
-            RIH_RW_TERM(acc1, 0, 1)
-#undef RIH_RW_TERM
+            RIH_E2_MMA3(TM, TN, av, bv, acc, acc1)
         }
     };
 
@@ -1004,14 +840,7 @@ __global__ __launch_bounds__(NT, 2) void rows_kernel(const RowsArgs p) {
     float* stg = reinterpret_cast<float*>(smem) + wave * (32 * SLD);
     const float inv_a = 1.f / sa, inv_b = 1.f / sb;
     const int mbase = m0 + wm * (32 * TM), nbase = n0 + wn * (32 * TN);
-    float4 ssh[STATS ? TN : 1], ssum[STATS ? TN : 1], ssq[STATS ? TN : 1];
-    float scnt[STATS ? TN : 1];
-    if (STATS) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            ssh[j] = make_float4(0, 0, 0, 0); ssum[j] = make_float4(0, 0, 0, 0); ssq[j] = make_float4(0, 0, 0, 0); scnt[j] = 0.f;
-        }
-    }
+    RIH_E2_STATS_DECL(STATS, TN)
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -1024,9 +853,7 @@ __global__ __launch_bounds__(NT, 2) void rows_kernel(const RowsArgs p) {
                                                              j * 32 + (lane & 7) * 4);
             }
             if (i + j > 0) __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                stg[((r & 3) + 8 * (r >> 2) + 4 * lhi) * SLD + l31] = fmaf(acc1[i][j][r], 0x1p-11f, acc[i][j][r]) * inv_a * inv_b;
+            RIH_E2_STAGE(stg, SLD, acc[i][j], acc1[i][j], inv_a, inv_b, l31, lhi)
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -1035,13 +862,7 @@ __global__ __launch_bounds__(NT, 2) void rows_kernel(const RowsArgs p) {
                 if (RES) { v.x += rv[q].x; v.y += rv[q].y; v.z += rv[q].z; v.w += rv[q].w; }
                 if (p.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                 *reinterpret_cast<float4*>(p.c + (long long)(mbase + i * 32 + row) * p.ldc + nbase + j * 32 + c4) = v;
-                if (STATS) {
-                    if (scnt[j] == 0.f) ssh[j] = v;
-                    scnt[j] += 1.f;
-                    const float dx = v.x - ssh[j].x, dy = v.y - ssh[j].y, dz = v.z - ssh[j].z, dw = v.w - ssh[j].w;
-                    ssum[j].x += dx; ssum[j].y += dy; ssum[j].z += dz; ssum[j].w += dw;
-                    ssq[j].x += dx * dx; ssq[j].y += dy * dy; ssq[j].z += dz * dz; ssq[j].w += dw * dw;
-                }
+                if (STATS) RIH_E2_STATS_ADD(j, v)
             }
         }
     }
@@ -1049,29 +870,7 @@ __global__ __launch_bounds__(NT, 2) void rows_kernel(const RowsArgs p) {
         const long long rblk = mbase / (32 * TM);
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            float n = scnt[j];
-            const float in = n > 0.f ? 1.f / n : 0.f;
-            float4 mean = make_float4(ssh[j].x + ssum[j].x * in, ssh[j].y + ssum[j].y * in, ssh[j].z + ssum[j].z * in,
-                                      ssh[j].w + ssum[j].w * in);
-            float4 m2 = make_float4(ssq[j].x - ssum[j].x * ssum[j].x * in, ssq[j].y - ssum[j].y * ssum[j].y * in,
-                                    ssq[j].z - ssum[j].z * ssum[j].z * in, ssq[j].w - ssum[j].w * ssum[j].w * in);
-#pragma unroll
-            for (int o = 8; o < 64; o <<= 1) {
-                const float nbr = __shfl_xor(n, o, 64);
-                const float nt = n + nbr;
-                const float wb = nt > 0.f ? nbr / nt : 0.f;
-                const float cf = n * wb;
-#define RIH_RW_MERGE(c_)                                                              \
-    {                                                                                 \
-        const float mb = __shfl_xor(mean.c_, o, 64), qb = __shfl_xor(m2.c_, o, 64);   \
-        const float dl = mb - mean.c_;                                                \
-        mean.c_ += dl * wb;                                                           \
-        m2.c_ += qb + dl * dl * cf;                                                   \
-    }
-                RIH_RW_MERGE(x) RIH_RW_MERGE(y) RIH_RW_MERGE(z) RIH_RW_MERGE(w)
-#undef RIH_RW_MERGE
-                n = nt;
-            }
+            RIH_E2_STATS_MERGE(j, mean, m2)
             if ((lane >> 3) == 0) {
                 const int nn = nbase + j * 32 + (lane & 7) * 4;
                 *reinterpret_cast<float4*>(p.stats + (rblk * 2 + 0) * p.N + nn) = mean;

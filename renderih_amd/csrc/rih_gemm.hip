@@ -9,17 +9,19 @@
 // MFMA operand fetch is one conflict-free ds_read_b32 per lane (lanes 0-31 -> consecutive m, lanes
 // 32-63 -> next k).  Global->register prefetch of tile t+1 is issued before the MFMAs of tile t.
 // blockIdx.x is remapped so that each XCD (private L2) works on a contiguous run of tiles.
+// The arithmetic of engine 2 (scale, two-term fp16 split, MFMA step, epilogue fold, column statistics), the XCD remap and the raw
+// buffer load are shared with rih_conv3.hip: rih_e2.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include "../../include/renderih_amd.h"
 #include "rih_hash.h"
+#include "rih_e2.h"
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -62,13 +64,6 @@ struct GemmArgs {
     unsigned aseg_bytes[3];
 };
 
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-    // bijective "each XCD gets a contiguous chunk" remap (blocks are dispatched round-robin over 8 XCDs)
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return base + (bid >> 3);
-}
-
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ void set_elem(float4& v, int e, float x) {
     if (e == 0) v.x = x; else if (e == 1) v.y = x; else if (e == 2) v.z = x; else v.w = x;
@@ -110,56 +105,8 @@ __device__ __forceinline__ void split2(float a, float b, unsigned& h, unsigned& 
 __device__ __forceinline__ int lds_row(int m) { return (m ^ ((m >> 4) & 1)) * 16; }
 __device__ __forceinline__ int lds_swz(int m) { return (m >> 2) & 3; }
 
-// ---- split engine 2 (ENGINE 2): fp32 operands are scaled by a power of two s (so that s * max|x| lies in [2^14, 2^15), well
-// inside the fp16 range) and split on the way into LDS into TWO fp16 planes, hi = fp16(s x) and lo = fp16((s x - hi) * 2^11)
-// (round-to-nearest both; |s x - hi - 2^-11 lo| <= 2^-23 |s x|, and lo keeps its 11 bits down to |s x| = 2^-14 * 2^-11 thanks
-// to the 2^11 pre-scale -- the error-corrected tensor-core SGEMM scheme of Ootomo & Yokota).  The product is formed with THREE
-// v_mfma_f32_32x32x16_f16 per 32x32x16 block: hi*hi into one fp32 accumulator, hi*lo + lo*hi into a second one; the epilogue
-// combines acc0 + 2^-11 acc1 and undoes the operand scales (exact: powers of two).  The dropped lo*lo term is <= 2^-22
-// relative.  Half the matrix-pipe work (and energy) per fp32 FLOP of the six-product bf16 engine: 2.5 PF / 3 = 833 TF.
-// The scale comes from a device-resident upper bound of max|x| (GemmArgs.amax_a / amax_b: a bound block written by the kernel
-// that produced the operand, or by rih_absmax): any upper bound is correct, a loose one only costs range at the bottom (full 22-bit
-// precision for |x| >= 2^-29 * bound).
-__device__ __forceinline__ float e2_scale(const float* amax, bool at_least_one) {
-    if (amax == nullptr) return 1.f;
-    // the bound block: 64 partial maxima, one per 128-byte line (include/renderih_amd.h: rih_absmax) -- one vector load per
-    // wavefront and an xor-shuffle maximum; the result is wave-uniform
-    float a = amax[(threadIdx.x & 63) * (RIH_BOUND_FLOATS / 64)];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
-    a = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(a)));
-    if (at_least_one) a = fmaxf(a, 1.f);            // the all-ones row of a weight-gradient's A operand must stay in range
-    const int e = (int)((__float_as_uint(a) >> 23) & 0xffu);
-    if (e == 0 || e == 255) return 1.f;             // zero / denormal bound (an all-zero operand), or inf / NaN (garbage either way)
-    int se = 268 - e;                               // 2^(14 - (e - 127)), biased
-    se = se > 253 ? 253 : se;                       // keep 1/s a normal number
-    return __uint_as_float((unsigned)se << 23);
-}
-__device__ __forceinline__ unsigned pk_f16(float a, float b) {
-    const f16x2 v = {(_Float16)a, (_Float16)b};     // RNE; a in the low half
-    return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ void split2h(float a, float b, float s, unsigned& h, unsigned& l) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    // six mixed-precision FMAs per pair (hipcc's own selection for the C form below takes ten): the f16 result of
-    // v_fma_mix{lo,hi}_f16 is the RNE conversion of the exact product (a power-of-two scaling), v_fma_mix_f32 reads the f16 half
-    // back as an addend, so the residual a*s - hi is one instruction and exact
-    float ra, rb;
-    const float k2048 = 2048.f;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(h) : "v"(a), "s"(s));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(h) : "v"(b), "s"(s));
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel_hi:[0,0,1]" : "=v"(ra) : "v"(a), "s"(s), "v"(h));
-    asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(rb) : "v"(b), "s"(s), "v"(h));
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(l) : "v"(ra), "s"(k2048));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(l) : "v"(rb), "s"(k2048));
-#else       /* host build of tests/hipcpu: the same arithmetic in C */
-    a *= s;
-    b *= s;
-    const f16x2 hv = {(_Float16)a, (_Float16)b};
-    h = __builtin_bit_cast(unsigned, hv);
-    l = pk_f16((a - (float)hv.x) * 2048.f, (b - (float)hv.y) * 2048.f);        // the differences are exact in fp32
-#endif
-}
+// ---- split engine 2 (ENGINE 2): the two-term fp16 split with three MFMA products.  The scheme is described in rih_e2.h, which
+// holds its arithmetic (e2_scale, e2_split2h, RIH_E2_MMA3, RIH_E2_STAGE, RIH_E2_STATS_*) for this file and rih_conv3.hip.
 
 // Epilogue shared by the kernels below.  Accumulators -> LDS (one 32x32 block per wave at a time; the operand tiles are dead
 // by then) -> each lane owns 4 consecutive columns of a row: one 16-byte residual load and one 16-byte store per lane, 8 lanes
@@ -167,16 +114,14 @@ __device__ __forceinline__ void split2h(float a, float b, float s, unsigned& h, 
 // kernels is issue-bound (all CUs write their tiles in lock-step, MI355X_MICROARCH.md "epilogue store tail"): measured on the
 // B = 64 step, GEMM family 24.0 -> 22.3 ms (profiles/r02/bench_m14_wide_epilogue.log).
 // `stg`: this wave's 32 x SLD floats of LDS; the caller guarantees a __syncthreads() since the last operand read.
-constexpr int SLD = 36;             // floats per staged row: 32 + pad, keeps float4 alignment
-// STATS: also the per-column (mean, centred sum of squares M2) of the stored values over the wave's TM*32 rows -- shifted sums per
-// lane, Chan's pairwise merge across lanes: no E[x^2] - mean^2 cancellation -- written to p.stats[row block][2][N]; the BatchNorm
-// that follows the convolution merges the blocks in double (rih_bn_stats_from_blocks).  The training statistics then cost no
-// pass over the activation (csrc/rih_elem.hip: bn_stats_partial_kernel reads it once).
+// STATS: also the per-column (mean, centred sum of squares M2) of the stored values over the wave's TM*32 rows (RIH_E2_STATS_* of
+// rih_e2.h), written to p.stats[row block][2][N].  The training statistics then cost no pass over the activation
+// (csrc/rih_elem.hip: bn_stats_partial_kernel reads it once).
 // DROP (rih_gemm_desc.drop_p > 0; plain a_mode-0 GEMMs = nn.Linear): v = dropout(act(alpha acc + bias)) + R -- the mask stream
 // of rih_add_dropout over the output tensor (element index = offset from desc.C), so the fused form equals
 // rih_gemm followed by rih_add_dropout(R, ., p, seed) bit for bit and rih_dropout_bwd re-draws the same mask.
-// E2 (engine 2): the staged value is (acc + 2^-11 acc1) * inv_a * inv_b -- the correction accumulator folded in and the operand
-// scales undone (also for the raw split-K slabs, whose reduction knows nothing of scales).
+// E2 (engine 2): the block is staged by RIH_E2_STAGE -- the correction accumulator folded in and the operand scales undone (also
+// for the raw split-K slabs, whose reduction knows nothing of scales).
 template <int TM, int TN, bool STATS = false, bool DROP = false, bool E2 = false>
 __device__ __forceinline__ void store_tiles_wide(const GemmArgs& p, floatx16 (&acc)[TM][TN], float* stg, float* __restrict__ C,
                                                  const float* __restrict__ biasp, const float* __restrict__ Rp, int mbase,
@@ -187,13 +132,7 @@ __device__ __forceinline__ void store_tiles_wide(const GemmArgs& p, floatx16 (&a
     const int l31 = lane & 31, lhi = lane >> 5;
     unsigned long long drop_key = 0ull;
     if (DROP) drop_key = rih_seed_key(p.drop_seed + (p.drop_seed_dev != nullptr ? *p.drop_seed_dev : 0ull));
-    // per lane and column block: shift (the lane's first stored row), sums of (v - shift) and of its square, row count
-    float4 ssh[STATS ? TN : 1], ssum[STATS ? TN : 1], ssq[STATS ? TN : 1];
-    float scnt[STATS ? TN : 1];
-    if (STATS) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j) { ssh[j] = zero4(); ssum[j] = zero4(); ssq[j] = zero4(); scnt[j] = 0.f; }
-    }
+    RIH_E2_STATS_DECL(STATS, TN)
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -202,11 +141,11 @@ __device__ __forceinline__ void store_tiles_wide(const GemmArgs& p, floatx16 (&a
             // store their blocks without waiting for each other -- round 4; before: two workgroup barriers per 32x32 block;
             // same-box A/B 1936.8 / 1937.1 against 1937.2 / 1932.5 images/s: neutral, kept as the simpler form)
             if (i + j > 0) __builtin_amdgcn_wave_barrier();         // the previous block has been read back
+            if (E2) {
+                RIH_E2_STAGE(stg, SLD, acc[i][j], acc1[i][j], inv_a, inv_b, l31, lhi)
+            } else {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float v = acc[i][j][r];
-                if (E2) v = fmaf(acc1[i][j][r], 0x1p-11f, v) * inv_a * inv_b;
-                stg[((r & 3) + 8 * (r >> 2) + 4 * lhi) * SLD + l31] = v;
+                for (int r = 0; r < 16; ++r) stg[((r & 3) + 8 * (r >> 2) + 4 * lhi) * SLD + l31] = acc[i][j][r];
             }
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -258,45 +197,15 @@ __device__ __forceinline__ void store_tiles_wide(const GemmArgs& p, floatx16 (&a
                     if (n + 2 < p.N) crow[2] = v.z;
                     if (n + 3 < p.N) crow[3] = v.w;
                 }
-                if (STATS) {        // (columns past N are never written out below)
-                    if (scnt[j] == 0.f) ssh[j] = v;
-                    scnt[j] += 1.f;
-                    const float dx = v.x - ssh[j].x, dy = v.y - ssh[j].y, dz = v.z - ssh[j].z, dw = v.w - ssh[j].w;
-                    ssum[j].x += dx; ssum[j].y += dy; ssum[j].z += dz; ssum[j].w += dw;
-                    ssq[j].x += dx * dx; ssq[j].y += dy * dy; ssq[j].z += dz * dz; ssq[j].w += dw * dw;
-                }
+                if (STATS) RIH_E2_STATS_ADD(j, v)       // (columns past N are never written out below)
             }
         }
     }
     if (STATS) {
-        // a lane holds (count, mean, centred sum of squares) of its <= 4*TM rows per column; the eight row-lanes (lane >> 3)
-        // are merged pairwise with Chan's formula (three xor-shuffle rounds), lane >> 3 == 0 writes the block's (mean, M2)
         const long long rb = mbase / (TM * 32);
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-            float n = scnt[j];
-            const float inv = n > 0.f ? 1.f / n : 0.f;
-            float4 mean = make_float4(ssh[j].x + ssum[j].x * inv, ssh[j].y + ssum[j].y * inv, ssh[j].z + ssum[j].z * inv,
-                                      ssh[j].w + ssum[j].w * inv);
-            float4 m2 = make_float4(ssq[j].x - ssum[j].x * ssum[j].x * inv, ssq[j].y - ssum[j].y * ssum[j].y * inv,
-                                    ssq[j].z - ssum[j].z * ssum[j].z * inv, ssq[j].w - ssum[j].w * ssum[j].w * inv);
-#pragma unroll
-            for (int o = 8; o < 64; o <<= 1) {
-                const float nb = __shfl_xor(n, o, 64);
-                const float nt = n + nb;
-                const float wb = nt > 0.f ? nb / nt : 0.f;          // weight of the partner's mean
-                const float cf = n * wb;                            // n * nb / nt
-#define RIH_MERGE(c_)                                                        \
-    {                                                                        \
-        const float mb = __shfl_xor(mean.c_, o, 64), qb = __shfl_xor(m2.c_, o, 64); \
-        const float dl = mb - mean.c_;                                       \
-        mean.c_ += dl * wb;                                                  \
-        m2.c_ += qb + dl * dl * cf;                                          \
-    }
-                RIH_MERGE(x) RIH_MERGE(y) RIH_MERGE(z) RIH_MERGE(w)
-#undef RIH_MERGE
-                n = nt;
-            }
+            RIH_E2_STATS_MERGE(j, mean, m2)
             const int nn = nbase + j * 32 + (lane & 7) * 4;
             if ((lane >> 3) == 0 && nn < p.N && mbase < p.M) {
                 float* s0 = p.stats + (rb * 2 + 0) * p.N + nn;
@@ -769,17 +678,9 @@ int launch_tile(const GemmArgs& a, int a_mode, int b_mode, int engine, dim3 grid
 // Preconditions (checked by rih_gemm, which otherwise uses the general kernel): 16-byte aligned operands, upS == 1,
 // conv A-gather (AMODE 0, not plain) needs Cin % 32 == 0 and KH*KW <= 32; transpose gather (AMODE 1, not plain)
 // needs Wo % 4 == 0; K % 4 == 0; N % 4 == 0 for BMODE 0; operand slices < 2 GiB.
-constexpr unsigned OOB = 0x80000000u;
-
-__device__ __forceinline__ float4 bload4(__amdgpu_buffer_rsrc_t r, unsigned off) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
-    return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-
 // The kernel body takes the block coordinates as arguments: gemm_split_kernel passes blockIdx / gridDim, the grouped launch
 // (gemm_split_multi_kernel, rih_gemm_multi) the coordinates of a block inside ITS problem of a descriptor table.
-// ENG 2: the two-term fp16 split (three MFMA products, see e2_scale / split2h above) instead of the three-term bf16 one; same
+// ENG 2: the two-term fp16 split (three MFMA products, see rih_e2.h) instead of the three-term bf16 one; same
 // loaders, LDS layout (two planes instead of three) and epilogue.
 template <int BM, int BN, int AMODE, int BMODE, bool PLAIN, bool STATS = false, bool DROP = false, int ENG = 1,
           bool SEG = false>
@@ -1036,8 +937,8 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& p, const int blk
     auto put4 = [](unsigned* u, int plane, float sc, float x0, float x1, float x2, float x3) {
         if (ENG == 2) {
             unsigned h0, l0, h1, l1;
-            split2h(x0, x1, sc, h0, l0);
-            split2h(x2, x3, sc, h1, l1);
+            e2_split2h(x0, x1, sc, h0, l0);
+            e2_split2h(x2, x3, sc, h1, l1);
             *reinterpret_cast<uint2*>(u) = make_uint2(h0, h1);
             *reinterpret_cast<uint2*>(u + plane) = make_uint2(l0, l1);
         } else {
@@ -1052,7 +953,7 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& p, const int blk
     auto put2 = [](unsigned* u, int plane, float sc, float x0, float x1) {
         if (ENG == 2) {
             unsigned h, l;
-            split2h(x0, x1, sc, h, l);
+            e2_split2h(x0, x1, sc, h, l);
             u[0] = h;
             u[plane] = l;
         } else {
@@ -1147,13 +1048,7 @@ __device__ __forceinline__ void gemm_split_body(const GemmArgs& p, const int blk
                             for (int jj = 0; jj < TN; ++jj)
                                 bv[pl][jj] = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4*>(Bs + pl * PLANE_B + sb_off[s] + jj * 512));
                         }
-#define RIH_E2_TERM(ACC_, PA_, PB_)                                                                               \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int jj = 0; jj < TN; ++jj) ACC_[i][jj] = \
-        __builtin_amdgcn_mfma_f32_32x32x16_f16(av[PA_][i], bv[PB_][jj], ACC_[i][jj], 0, 0, 0);
-                        RIH_E2_TERM(acc1, 1, 0)
-                        RIH_E2_TERM(acc, 0, 0)
-                        RIH_E2_TERM(acc1, 0, 1)
-#undef RIH_E2_TERM
+                        RIH_E2_MMA3(TM, TN, av, bv, acc, acc1)
                     }
                 } else {
 #pragma unroll

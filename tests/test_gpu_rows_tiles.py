@@ -161,7 +161,7 @@ def _tid(t):
 @pytest.mark.parametrize('K', [64, 96, 256])            # two k-tiles (the minimum), three (odd), eight
 @pytest.mark.parametrize('tile', TILES, ids=_tid)
 def test_tile_epilogue_trip_count(tile, K, epi):
-    """Forward weight form, 3 x 2 = 6 workgroups (not a multiple of 8: the remainder branch of xcd_remap_c3)."""
+    """Forward weight form, 3 x 2 = 6 workgroups (not a multiple of 8: the remainder branch of xcd_remap)."""
     check_rows_tile(tile, (3, 2), K, epi)
 
 
@@ -181,7 +181,7 @@ def test_tile_more_trip_counts(tile, K, epi):
 
 
 @pytest.mark.parametrize('epi', ['stats', 'res'])
-@pytest.mark.parametrize('grid', [(1, 1), (5, 2)], ids=_tid)    # a single workgroup; ten: q = 1, r = 2 in xcd_remap_c3
+@pytest.mark.parametrize('grid', [(1, 1), (5, 2)], ids=_tid)    # a single workgroup; ten: q = 1, r = 2 in xcd_remap
 @pytest.mark.parametrize('tile', TILES, ids=_tid)
 def test_tile_more_grids(tile, grid, epi):
     check_rows_tile(tile, grid, 96, epi)
