@@ -194,10 +194,10 @@ def cached_bound(t):
     return ent[0] if (ent is not None and ent[1] == t._version and ent[2] == _BOUND_EPOCH) else None
 
 
-def inherit_bound(y, *xs):
+def inherit_bound(y, *xs, slack=None):
     """y's values are bounded by the largest magnitude among xs (selections / convex combinations / a concatenation of them):
     hand their bound on when every x carries one (engine 2 only; a missing bound leaves y without one -- bound_of then
-    measures it)."""
+    measures it).  `slack` (> 1) widens the bound handed on, for an operation that rounds (see BILINEAR_SLACK)."""
     if ENGINE != 2:
         return y
     slots = [cached_bound(x) for x in xs]
@@ -206,6 +206,8 @@ def inherit_bound(y, *xs):
     b = slots[0]
     for s_ in slots[1:]:
         b = torch.maximum(b, s_)
+    if slack is not None:
+        b = b * slack
     return set_bound(y, b)
 
 
@@ -1772,12 +1774,21 @@ class UpsampleBilinearFn(torch.autograd.Function):
         return dx, None
 
 
+# A bilinear sample is a convex combination of four corners only up to rounding: rih_upsample_bilinear_fwd computes
+# hl0 * (wl0 * a + lw * b) + lh * (wl0 * c + lw * d) with wl0 = fl(1 - lw) <= (1 - lw) + 2^-25 (likewise hl0) and at most four
+# roundings on the way to each output (product, sum, product, sum; fewer where the compiler contracts), so
+# |y| <= max|x| * (1 + 2^-25)^2 * (1 + 2^-24)^4 < max|x| * (1 + 2^-21): four equal corners of 0.1 give 0.10000001.  The input's
+# bound handed on as it is would lie BELOW max|y| (tests/test_gpu_bounds.py); it is handed on times 1 + 2^-20, which after its
+# own rounding is still > 1 + 2^-21.
+BILINEAR_SLACK = 1.0 + 2.0 ** -20
+
+
 def upsample_bilinear(x, factor):
-    return inherit_bound(UpsampleBilinearFn.apply(x, factor), x)        # convex combinations of input values
+    return inherit_bound(UpsampleBilinearFn.apply(x, factor), x, slack=BILINEAR_SLACK)
 
 
 def upsample_bilinear2x(x):
-    return inherit_bound(UpsampleBilinearFn.apply(x, 2), x)
+    return inherit_bound(UpsampleBilinearFn.apply(x, 2), x, slack=BILINEAR_SLACK)
 
 
 class NearestUpAddFn(torch.autograd.Function):

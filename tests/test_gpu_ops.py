@@ -22,6 +22,12 @@ def rnd(*shape, seed=0, scale=1.0):
     return torch.randn(*shape, generator=g) * scale
 
 
+def scaled(t, s):
+    """t * s, and t itself at s == 1: the keyword scales xs / ws / gs of the engine-2 test bodies (activations, weights, upstream
+    gradients; tests/test_gpu_e2_range.py) leave the default data bit for bit as it was."""
+    return t if s == 1.0 else t * s
+
+
 def nhwc(x):
     return x.permute(0, 2, 3, 1).contiguous()
 
@@ -53,18 +59,18 @@ CONV_CASES = [
 
 
 @pytest.mark.parametrize('case', CONV_CASES)
-def test_conv2d(case):
+def test_conv2d(case, xs=1.0, ws=1.0, gs=1.0):
     from renderih_amd import ops
     N, H, W, Cin, Cout, k, s, p, bias, relu = case
-    x = rnd(N, Cin, H, W, seed=1)
-    w = rnd(Cout, Cin, k, k, seed=2, scale=1.0 / math.sqrt(Cin * k * k))
-    b = rnd(Cout, seed=3) if bias else None
+    x = scaled(rnd(N, Cin, H, W, seed=1), xs)
+    w = scaled(rnd(Cout, Cin, k, k, seed=2, scale=1.0 / math.sqrt(Cin * k * k)), ws)
+    b = scaled(rnd(Cout, seed=3), xs * ws) if bias else None
     xr, wr = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
     br = b.clone().requires_grad_(True) if bias else None
     yr = F.conv2d(xr, wr, br, stride=s, padding=p)
     if relu:
         yr = F.relu(yr)
-    gy = rnd(*yr.shape, seed=4)
+    gy = scaled(rnd(*yr.shape, seed=4), gs)
     yr.backward(gy)
 
     d = dev()
@@ -88,7 +94,7 @@ def test_conv2d(case):
 @pytest.mark.parametrize('case', [(2, 16, 16, (128, 128, 256), 256, True), (3, 9, 7, (32, 64), 40, False),
                                   (2, 8, 8, (128, 128, 1024, 32), 256, True), (1, 33, 5, (64, 32, 96), 128, False),
                                   (2, 8, 8, (64, 32), 64, 'ungated'), (1, 6, 6, (32, 40), 32, True)])
-def test_conv1x1_cat(case, engine, monkeypatch=None):
+def test_conv1x1_cat(case, engine, monkeypatch=None, xs=1.0, ws=1.0, gs=1.0):
     """ops.conv1x1_cat (segmented GEMM operand, rih_gemm_desc.a_seg): the 1x1 convolution of a channel concatenation read in place
     -- output, the statistics epilogue, every part's gradient and the weight gradient (written as column slices by the reduction)
     against F.conv2d on the materialised concatenation; engines 1 and 2, two to four parts, ragged row counts, N tails.  Engine 0
@@ -102,15 +108,15 @@ def test_conv1x1_cat(case, engine, monkeypatch=None):
     saved = ops.ENGINE
     ops.ENGINE = engine
     try:
-        parts = [rnd(N, c, H, W, seed=11 + i) * (1.0 + 3.0 * i) for i, c in enumerate(Cs)]
+        parts = [scaled(rnd(N, c, H, W, seed=11 + i) * (1.0 + 3.0 * i), xs) for i, c in enumerate(Cs)]
         Cin = sum(Cs)
-        w = rnd(Cout, Cin, 1, 1, seed=2, scale=1.0 / math.sqrt(Cin))
+        w = scaled(rnd(Cout, Cin, 1, 1, seed=2, scale=1.0 / math.sqrt(Cin)), ws)
         pr = [t.clone().requires_grad_(True) for t in parts]
         wr = w.clone().requires_grad_(True)
         yr = F.conv2d(torch.cat(pr, dim=1), wr)
         if relu:
             yr = F.relu(yr)
-        gy = rnd(*yr.shape, seed=4)
+        gy = scaled(rnd(*yr.shape, seed=4), gs)
         if relu and not ungated:
             gy = gy * (yr > 0).float()          # the consumer (BatchNorm with input_relu) hands back a gradient gated by y > 0
         yr.backward(gy)
@@ -146,7 +152,7 @@ HALO_CASES = [(2, 16, 32, 64, 128, False, True), (1, 8, 64, 32, 64, True, True),
 
 
 @pytest.mark.parametrize('case', HALO_CASES)
-def test_conv3x3_halo(case, monkeypatch=None):
+def test_conv3x3_halo(case, monkeypatch=None, xs=1.0, ws=1.0, gs=1.0):
     """csrc/rih_conv3.hip through ops.conv2d (ops.HALO3, engine 2): stride-1 3x3 convolution with the input halo resident in LDS
     and pre-split (H2) weights -- output (+ ReLU), the BatchNorm statistics of its epilogue, the data gradient (the same kernel on
     flipped weights) and the weight gradient (rih_gemm) against F.conv2d in fp64; and equal to the tap-by-tap implicit GEMM
@@ -156,13 +162,13 @@ def test_conv3x3_halo(case, monkeypatch=None):
     saved = (ops.ENGINE, ops.HALO3)
     ops.ENGINE = 2
     try:
-        x = rnd(N, Cin, H, W, seed=21) * 3.0
-        w = rnd(Cout, Cin, 3, 3, seed=22, scale=1.0 / math.sqrt(9 * Cin))
+        x = scaled(rnd(N, Cin, H, W, seed=21) * 3.0, xs)
+        w = scaled(rnd(Cout, Cin, 3, 3, seed=22, scale=1.0 / math.sqrt(9 * Cin)), ws)
         xr, wr = x.double().clone().requires_grad_(True), w.double().clone().requires_grad_(True)
         yr = F.conv2d(xr, wr, padding=1)
         if relu:
             yr = F.relu(yr)
-        gy = rnd(*yr.shape, seed=23)
+        gy = scaled(rnd(*yr.shape, seed=23), gs)
         yr.backward(gy.double())
         d = dev()
         outs = {}
@@ -197,7 +203,7 @@ HALO_SKIP_CASES = [(2, 8, 32, 32, 32), (1, 16, 16, 64, 64), (2, 16, 32, 128, 128
 
 
 @pytest.mark.parametrize('case', HALO_SKIP_CASES)
-def test_conv3x3_halo_with_skip_gradient(case):
+def test_conv3x3_halo_with_skip_gradient(case, xs=1.0, ws=1.0, gs=1.0):
     """The data gradient of a residual block's FIRST 3x3 convolution (HRNet's BasicBlock.conv1 through ops.conv2d_skip): the skip
     path's gradient joins in the halo kernel's epilogue (rih_conv3_desc.r, ABI 19; ops.HALO3_RES) -- dx, dw and the forward against
     fp64 with the skip contribution, and against the tiled kernel's residual epilogue (HALO3_RES off).  The launch really is the halo
@@ -215,12 +221,12 @@ def test_conv3x3_halo_with_skip_gradient(case):
         return ok
     ops.conv3x3_halo = spy
     try:
-        x = rnd(N, Cin, H, W, seed=51) * 2.0
-        w = rnd(Cout, Cin, 3, 3, seed=52, scale=1.0 / math.sqrt(9 * Cin))
+        x = scaled(rnd(N, Cin, H, W, seed=51) * 2.0, xs)
+        w = scaled(rnd(Cout, Cin, 3, 3, seed=52, scale=1.0 / math.sqrt(9 * Cin)), ws)
         xr, wr = x.double().clone().requires_grad_(True), w.double().clone().requires_grad_(True)
         yr = F.conv2d(xr, wr, padding=1)
-        gy, gs = rnd(*yr.shape, seed=53), rnd(*x.shape, seed=54)
-        (yr * gy.double()).sum().add((xr * gs.double()).sum()).backward()     # the skip path contributes gs to dx
+        gy, gk = scaled(rnd(*yr.shape, seed=53), gs), scaled(rnd(*x.shape, seed=54), gs)
+        (yr * gy.double()).sum().add((xr * gk.double()).sum()).backward()     # the skip path contributes gk to dx
         d = dev()
         outs = {}
         for res in (True, False):
@@ -229,7 +235,7 @@ def test_conv3x3_halo_with_skip_gradient(case):
             xg = nhwc(x).contiguous().to(d).requires_grad_(True)
             wg = w.clone().to(d).requires_grad_(True)
             yg, idt = ops.conv2d_skip(xg, wg, None, stride=1, pad=1, relu=False)
-            ((yg * nhwc(gy).contiguous().to(d)).sum() + (idt * nhwc(gs).contiguous().to(d)).sum()).backward()
+            ((yg * nhwc(gy).contiguous().to(d)).sum() + (idt * nhwc(gk).contiguous().to(d)).sum()).backward()
             outs[res] = (nchw(yg).detach().cpu(), nchw(xg.grad).cpu(), wg.grad.cpu())
             assert_close(outs[res][0], yr.float(), 1e-4, 1e-5, 'halo skip %s y %s' % (res, case,))
             assert_close(outs[res][1], xr.grad.float(), 1e-4, 1e-5, 'halo skip %s dx %s' % (res, case,))
@@ -270,7 +276,7 @@ PANEL_CASES = [(2, 64, 64, 64, 256, False, True), (1, 64, 64, 128, 512, False, T
 
 
 @pytest.mark.parametrize('case', PANEL_CASES)
-def test_panel_1x1(case, monkeypatch=None):
+def test_panel_1x1(case, monkeypatch=None, xs=1.0, ws=1.0, gs=1.0):
     """csrc/rih_conv3.hip panel_kernel through ops.conv2d / ops.conv2d_skip (ops.PANEL, engine 2): 1x1 convolutions with K = 64 / 128
     as persistent streaming workgroups -- forward (+ ReLU, + BatchNorm statistics), the data gradient WITH the skip path's gradient
     as residual (conv2d_skip: Bottleneck.conv1), the weight gradient (rih_gemm) -- against fp64, and against the tiled kernels
@@ -286,14 +292,14 @@ def test_panel_1x1(case, monkeypatch=None):
                 and lda % 4 == 0)
     ops._panel_ok = ok_small
     try:
-        x = rnd(N, Cin, H, W, seed=31) * 2.0
-        w = rnd(Cout, Cin, 1, 1, seed=32, scale=1.0 / math.sqrt(Cin))
+        x = scaled(rnd(N, Cin, H, W, seed=31) * 2.0, xs)
+        w = scaled(rnd(Cout, Cin, 1, 1, seed=32, scale=1.0 / math.sqrt(Cin)), ws)
         xr, wr = x.double().clone().requires_grad_(True), w.double().clone().requires_grad_(True)
         yr = F.conv2d(xr, wr)
         if relu:
             yr = F.relu(yr)
-        gy, gs = rnd(*yr.shape, seed=33), rnd(*x.shape, seed=34)
-        (yr * gy.double()).sum().add((xr * gs.double()).sum()).backward()     # the skip path contributes gs to dx
+        gy, gk = scaled(rnd(*yr.shape, seed=33), gs), scaled(rnd(*x.shape, seed=34), gs)
+        (yr * gy.double()).sum().add((xr * gk.double()).sum()).backward()     # the skip path contributes gk to dx
         d = dev()
         outs = {}
         for panel in (True, False):
@@ -302,7 +308,7 @@ def test_panel_1x1(case, monkeypatch=None):
             wg = w.clone().to(d).requires_grad_(True)
             holder = ops.StatsHolder() if want_stats else None
             yg, idt = ops.conv2d_skip(xg, wg, None, stride=1, pad=0, relu=relu, stats=holder)
-            ((yg * nhwc(gy).contiguous().to(d)).sum() + (idt * nhwc(gs).contiguous().to(d)).sum()).backward()
+            ((yg * nhwc(gy).contiguous().to(d)).sum() + (idt * nhwc(gk).contiguous().to(d)).sum()).backward()
             outs[panel] = (nchw(yg).detach().cpu(), nchw(xg.grad).cpu(), wg.grad.cpu())
             assert_close(outs[panel][0], yr.float(), 1e-4, 1e-5, 'panel %s y %s' % (panel, case,))
             assert_close(outs[panel][1], xr.grad.float(), 1e-4, 1e-5, 'panel %s dx %s' % (panel, case,))
@@ -331,7 +337,7 @@ ROWS_CASES = [(2, 16, 16, 256, 64, False, True), (1, 16, 8, 96, 128, True, True)
 
 
 @pytest.mark.parametrize('case', ROWS_CASES)
-def test_rows_1x1(case, monkeypatch=None):
+def test_rows_1x1(case, monkeypatch=None, xs=1.0, ws=1.0, gs=1.0):
     """csrc/rih_conv3.hip rows_kernel through ops.conv2d / ops.conv2d_skip (ops.ROWS, engine 2): 1x1 convolutions with a long reduction
     as 512-thread workgroups with three LDS-DMA-staged stages of H2 weight planes, two A stages in LDS and the A prefetch in registers -- forward (+ ReLU, + BatchNorm statistics), the
     data gradient WITH the skip path's gradient as residual (conv2d_skip: Bottleneck.conv1), the weight gradient (rih_gemm) --
@@ -344,14 +350,14 @@ def test_rows_1x1(case, monkeypatch=None):
     saved = (ops.ENGINE, ops.ROWS, ops.ROWS_MINK, ops.ROWS_MIN_WGS, ops.PANEL, ops.ROWS_MIN_M, ops.ROWS_MIN_N)
     ops.ENGINE, ops.ROWS_MINK, ops.ROWS_MIN_WGS, ops.PANEL, ops.ROWS_MIN_M, ops.ROWS_MIN_N = 2, 64, 1, False, 1, 64
     try:
-        x = rnd(N, Cin, H, W, seed=41) * 2.0
-        w = rnd(Cout, Cin, 1, 1, seed=42, scale=1.0 / math.sqrt(Cin))
+        x = scaled(rnd(N, Cin, H, W, seed=41) * 2.0, xs)
+        w = scaled(rnd(Cout, Cin, 1, 1, seed=42, scale=1.0 / math.sqrt(Cin)), ws)
         xr, wr = x.double().clone().requires_grad_(True), w.double().clone().requires_grad_(True)
         yr = F.conv2d(xr, wr)
         if relu:
             yr = F.relu(yr)
-        gy, gs = rnd(*yr.shape, seed=43), rnd(*x.shape, seed=44)
-        (yr * gy.double()).sum().add((xr * gs.double()).sum()).backward()     # the skip path contributes gs to dx
+        gy, gk = scaled(rnd(*yr.shape, seed=43), gs), scaled(rnd(*x.shape, seed=44), gs)
+        (yr * gy.double()).sum().add((xr * gk.double()).sum()).backward()     # the skip path contributes gk to dx
         d = dev()
         outs = {}
         for rows in (True, False):
@@ -361,7 +367,7 @@ def test_rows_1x1(case, monkeypatch=None):
             wg = w.clone().to(d).requires_grad_(True)
             holder = ops.StatsHolder() if want_stats else None
             yg, idt = ops.conv2d_skip(xg, wg, None, stride=1, pad=0, relu=relu, stats=holder)
-            ((yg * nhwc(gy).contiguous().to(d)).sum() + (idt * nhwc(gs).contiguous().to(d)).sum()).backward()
+            ((yg * nhwc(gy).contiguous().to(d)).sum() + (idt * nhwc(gk).contiguous().to(d)).sum()).backward()
             outs[rows] = (nchw(yg).detach().cpu(), nchw(xg.grad).cpu(), wg.grad.cpu())
             assert_close(outs[rows][0], yr.float(), 1e-4, 1e-5, 'rows %s y %s' % (rows, case,))
             assert_close(outs[rows][1], xr.grad.float(), 1e-4, 1e-5, 'rows %s dx %s' % (rows, case,))
@@ -470,7 +476,7 @@ def test_rows_kernel_is_taken_and_falls_back(monkeypatch):
     assert int(ops._L().rih_rows_ok(C.byref(pd))) == 1
 
 
-def test_grouped_weight_gradients_on_128x64_tiles(monkeypatch):
+def test_grouped_weight_gradients_on_128x64_tiles(monkeypatch, xs=1.0, ws=1.0, gs=1.0):
     """ops.WGRAD_T1 (round 6): weight gradients with 33..64 output channels on a large map ride in the grouped launch on 128 x 64
     tiles of engine 2 (rih_gemm_multi variant 64 + 8 + 4 + plain) -- 3 x 3 and 1 x 1 convolutions, with the 64 x 64-tile path and fp64
     as references; bit-reproducible from run to run."""
@@ -478,11 +484,11 @@ def test_grouped_weight_gradients_on_128x64_tiles(monkeypatch):
     monkeypatch.setattr(ops, 'ENGINE', 2)
     monkeypatch.setattr(ops, 'WGRAD_T1_MINK', 512)
     d = dev()
-    xs = [rnd(2, 64, 16, 32, seed=61), rnd(2, 128, 16, 32, seed=66)]
-    gys = [rnd(2, 64, 16, 32, seed=62), rnd(2, 48, 16, 32, seed=63)]
-    ws = [rnd(64, 64, 3, 3, seed=64, scale=0.05), rnd(48, 128, 1, 1, seed=65, scale=0.1)]
+    xl = [scaled(rnd(2, 64, 16, 32, seed=61), xs), scaled(rnd(2, 128, 16, 32, seed=66), xs)]
+    gys = [scaled(rnd(2, 64, 16, 32, seed=62), gs), scaled(rnd(2, 48, 16, 32, seed=63), gs)]
+    wl = [scaled(rnd(64, 64, 3, 3, seed=64, scale=0.05), ws), scaled(rnd(48, 128, 1, 1, seed=65, scale=0.1), ws)]
     refs = []
-    for x, w, gy, pad in zip(xs, ws, gys, (1, 0)):
+    for x, w, gy, pad in zip(xl, wl, gys, (1, 0)):
         wr = w.double().clone().requires_grad_(True)
         F.conv2d(x.double(), wr, padding=pad).backward(gy.double())
         refs.append(wr.grad.float())
@@ -497,8 +503,8 @@ def test_grouped_weight_gradients_on_128x64_tiles(monkeypatch):
     for t1 in (True, False, True):
         monkeypatch.setattr(ops, 'WGRAD_T1', t1)
         del seen[:]
-        xg = [nhwc(x).contiguous().to(d) for x in xs]
-        wg = [w.clone().to(d).requires_grad_(True) for w in ws]
+        xg = [nhwc(x).contiguous().to(d) for x in xl]
+        wg = [w.clone().to(d).requires_grad_(True) for w in wl]
         with ops.deferred_reductions():
             ys = [ops.conv2d(xg[0], wg[0], None, stride=1, pad=1), ops.conv2d(xg[1], wg[1], None, stride=1, pad=0)]
             g = torch.autograd.grad([(y * nhwc(gy).contiguous().to(d)).sum() for y, gy in zip(ys, gys)], wg)
@@ -515,7 +521,7 @@ def test_grouped_weight_gradients_on_128x64_tiles(monkeypatch):
 
 
 @pytest.mark.parametrize('case', [(2, 32, 32, True, True), (16, 24, 40, False, True), (4, 16, 16, True, False)])
-def test_stem_conv(case, monkeypatch=None):
+def test_stem_conv(case, monkeypatch=None, xs=1.0, ws=1.0, gs=1.0):
     """csrc/rih_conv3.hip rows_kernel<STEM> through ops.conv2d (ops.STEM, engine 2): encoder.resnet.conv1 -- 7 x 7 / stride 2 / padding 3
     on the 4-channel padded image -- with the im2col loader (one tap of one output pixel = one float4; zero padding and the K = 196 ->
     224 tail by predication): output (+ ReLU), the BatchNorm statistics of its epilogue, the weight gradient (rih_gemm) against
@@ -525,13 +531,13 @@ def test_stem_conv(case, monkeypatch=None):
     saved = (ops.ENGINE, ops.STEM)
     ops.ENGINE = 2
     try:
-        x = rnd(N, 3, H, W, seed=51) * 2.0
-        w = rnd(64, 3, 7, 7, seed=52, scale=1.0 / math.sqrt(147.0))
+        x = scaled(rnd(N, 3, H, W, seed=51) * 2.0, xs)
+        w = scaled(rnd(64, 3, 7, 7, seed=52, scale=1.0 / math.sqrt(147.0)), ws)
         xr, wr = x.double(), w.double().clone().requires_grad_(True)
         yr = F.conv2d(xr, wr, stride=2, padding=3)
         if relu:
             yr = F.relu(yr)
-        gy = rnd(*yr.shape, seed=53)
+        gy = scaled(rnd(*yr.shape, seed=53), gs)
         yr.backward(gy.double())
         d = dev()
         outs = {}
@@ -1211,7 +1217,7 @@ def test_deferred_reductions_equal_immediate():
 
 
 @pytest.mark.parametrize('level', [1, 2])
-def test_grouped_weight_gradients(level):
+def test_grouped_weight_gradients(level, xs=1.0, ws=1.0, gs=1.0):
     """ops.GROUP_WGRAD: inside deferred_reductions() the weight-gradient GEMMs themselves are collected and run as ONE
     rih_gemm_multi launch per kernel variant at the end of the block, with fewer split-K slices per problem (the problems fill the
     chip together).  Decoder-like shapes -- paired nn.Linear (nb1 = 2, bias row), single nn.Linear, 3x3 / 1x1 convolutions with
@@ -1219,22 +1225,23 @@ def test_grouped_weight_gradients(level):
     and bit-reproducible from run to run."""
     from renderih_amd import ops
     d = dev()
-    x = nhwc(rnd(2, 32, 8, 8, seed=1)).to(d)
-    x64 = nhwc(rnd(2, 64, 8, 8, seed=21)).to(d)
-    convs = [(x, rnd(64, 32, 3, 3, seed=2, scale=0.1).to(d).requires_grad_(True), rnd(64, seed=3).to(d).requires_grad_(True), 1, 1),
-             (x, rnd(40, 32, 1, 1, seed=4, scale=0.2).to(d).requires_grad_(True), None, 1, 0),
-             (x64, rnd(136, 64, 3, 3, seed=22, scale=0.1).to(d).requires_grad_(True), None, 1, 1)]        # 576 x 136: 128x128 tiles
-    xl = rnd(2, 4, 66, 40, seed=5).to(d)                   # 264 rows per hand
-    wl, bl = rnd(2, 72, 40, seed=6, scale=0.2).to(d).requires_grad_(True), rnd(2, 72, seed=7).to(d).requires_grad_(True)
-    wm = [rnd(36 + 4 * i, 40, seed=8 + i, scale=0.2).to(d).requires_grad_(True) for i in range(5)]
-    bm = [rnd(36 + 4 * i, seed=40 + i).to(d).requires_grad_(True) for i in range(5)]
+    leaf = lambda t, s: scaled(t, s).to(d).requires_grad_(True)
+    x = nhwc(scaled(rnd(2, 32, 8, 8, seed=1), xs)).to(d)
+    x64 = nhwc(scaled(rnd(2, 64, 8, 8, seed=21), xs)).to(d)
+    convs = [(x, leaf(rnd(64, 32, 3, 3, seed=2, scale=0.1), ws), leaf(rnd(64, seed=3), xs * ws), 1, 1),
+             (x, leaf(rnd(40, 32, 1, 1, seed=4, scale=0.2), ws), None, 1, 0),
+             (x64, leaf(rnd(136, 64, 3, 3, seed=22, scale=0.1), ws), None, 1, 1)]        # 576 x 136: 128x128 tiles
+    xl = scaled(rnd(2, 4, 66, 40, seed=5), xs).to(d)       # 264 rows per hand
+    wl, bl = leaf(rnd(2, 72, 40, seed=6, scale=0.2), ws), leaf(rnd(2, 72, seed=7), xs * ws)
+    wm = [leaf(rnd(36 + 4 * i, 40, seed=8 + i, scale=0.2), ws) for i in range(5)]
+    bm = [leaf(rnd(36 + 4 * i, seed=40 + i), xs * ws) for i in range(5)]
 
     def loss():
         t = sum(ops.conv2d(xx, w, b, stride=s, pad=p).sum() * (i + 1) for i, (xx, w, b, s, p) in enumerate(convs))
         t = t + (ops.LinearPairFn.apply(xl, wl, None, bl, None, None, False) ** 2).sum()
         for i, (w, b) in enumerate(zip(wm, bm)):
             t = t + (ops.linear(xl[i % 2], w, b) * (0.5 + i)).sum()
-        return t
+        return scaled(t, gs)
 
     params = [w for _, w, _, _, _ in convs] + [convs[0][2], wl, bl] + wm + bm
     want = torch.autograd.grad([loss()], params)

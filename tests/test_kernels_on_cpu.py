@@ -12,6 +12,8 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, 'hipcpu'))
 
+import test_gpu_bounds as TB        # noqa: E402
+import test_gpu_e2_range as TR      # noqa: E402
 import test_gpu_loss as TL          # noqa: E402
 import test_gpu_mano as TMANO       # noqa: E402
 import test_gpu_ops as G            # noqa: E402
@@ -27,7 +29,7 @@ CPU = torch.device('cpu')
 @pytest.fixture(autouse=True)
 def _host_kernels(monkeypatch):
     from host_kernels import host_kernels_abi
-    for mod in (G, TL, TMANO, TRT):
+    for mod in (G, TB, TR, TL, TMANO, TRT):
         monkeypatch.setattr(mod, 'dev', lambda: CPU)
     with host_kernels_abi():
         yield
@@ -131,6 +133,97 @@ def test_stem_kernel(case):
 def test_grouped_wgrad_128x64_kernels(monkeypatch):
     """gemm_split_multi_kernel<128, 64, 1, 0, *, 2> (round 6) on the host harness."""
     G.test_grouped_weight_gradients_on_128x64_tiles(monkeypatch)
+
+
+# ------------------------------------------------------------------------------------ operand bounds, engine 2 off unit scale
+@pytest.mark.parametrize('n', TB.ABSMAX_N)
+def test_absmax_kernel_bounds(n):
+    """rih_absmax on the host harness: float4 and scalar paths, the n % 4 tail, more workgroups than slots."""
+    TB.check_absmax_n(n)
+
+
+def test_absmax_kernel_edges():
+    TB.test_absmax_zero_nan_and_merge()
+    TB.test_absmax_multi_refuses_empty_and_null()
+
+
+@pytest.mark.parametrize('count,with_big', [(1, True), (119, False), (120, False), (121, True), (241, False)])
+def test_absmax_multi_kernel_bounds(count, with_big):
+    """rih_absmax_multi on the host harness: list lengths around the pack of 120, a tensor beyond the 256-block cap."""
+    TB.check_absmax_multi(count, with_big)
+
+
+def test_absmax_kernels_against_the_emulator():
+    """The real rih_absmax / rih_absmax_multi against the numpy restatement in tests/abi_emulator.py: the same bound, bit for bit
+    (the emulator keeps it in the first slot word, the kernels spread it over 64), on fresh blocks and on blocks that hold a value."""
+    import numpy as np
+    from abi_emulator import EmulatedLib
+    from host_kernels import load
+    from renderih_amd._lib import AbsmaxDesc
+    host, emu = load(), EmulatedLib()
+    rs = np.random.RandomState(17)
+    sizes = [1, 3, 4, 5, 1023, 4097, 16 * 256 * 64 + 7] + [int(rs.randint(1, 9000)) for _ in range(124)]
+    bufs = []
+    for i, n in enumerate(sizes):
+        off = i % 2                                     # every second tensor starts one float off a 16-byte boundary
+        store = np.zeros(n + 8, np.float32)
+        base = (-store.ctypes.data // 4) % 4 + off
+        v = store[base:base + n]
+        v[:] = rs.randn(n) * 10.0 ** rs.randint(-6, 7)
+        if i % 5 == 0:
+            v[int(rs.randint(0, n))] = np.nan
+        bufs.append((store, v))
+    held = [np.float32(0 if i % 3 else abs(rs.randn()) * 10.0 ** rs.randint(-6, 7)) for i in range(len(sizes))]
+    outs = {}
+    for key, lib in (('host', host), ('emu', emu)):
+        single = np.zeros((len(sizes), TB.BF), np.float32)
+        multi = np.zeros((len(sizes), TB.BF), np.float32)
+        single[:, 0] = multi[:, 0] = held
+        arr = (AbsmaxDesc * len(sizes))()
+        for i, ((_, v), a) in enumerate(zip(bufs, arr)):
+            assert lib.rih_absmax(v.ctypes.data, v.size, single[i].ctypes.data, None) == 0
+            a.x, a.out, a.n = v.ctypes.data, multi[i].ctypes.data, v.size
+        assert lib.rih_absmax_multi(arr, len(sizes), None) == 0
+        outs[key] = (single.reshape(-1, 64, 32)[:, :, 0].max(1), multi.reshape(-1, 64, 32)[:, :, 0].max(1))
+    for a, b, what in zip(outs['host'], outs['emu'], ('rih_absmax', 'rih_absmax_multi')):
+        assert np.array_equal(a, b), (what, np.flatnonzero(a != b)[:8])
+    want = np.array([max(h, np.where(np.isnan(v), 0, np.abs(v)).max()) for h, (_, v) in zip(held, bufs)], np.float32)
+    assert np.array_equal(outs['host'][0], want)
+
+
+def test_batchnorm_kernel_bounds():
+    """The amax outputs of rih_bn_apply / rih_bn_bwd on the host harness: every option of tests/test_gpu_bounds.py."""
+    for shape in TB.BN_SHAPES:
+        for training in (True, False):
+            for relu in (False, True):
+                for res in (False, True):
+                    TB.check_bn_apply_bound(shape, training, relu, res)
+        for flags in range(4):
+            for relu, res, use_mask in ((False, False, True), (True, False, True), (True, True, True), (True, False, False),
+                                        (False, True, True), (True, True, False)):
+                TB.check_bn_bwd_bound(shape, flags, relu, res, use_mask)
+    TB.test_bn_apply_bound_with_a_negative_peak(False)
+    TB.test_bn_apply_bound_with_a_negative_peak(True)
+
+
+def test_bounds_through_the_ops_layer_and_into_the_convolutions():
+    TB.test_ops_batchnorm_leaves_the_kernels_bound_on_y_and_dx()
+    TB.test_inherited_bounds()
+    TB.test_bn_bound_feeds_the_halo_kernel_at_3e4()
+    TB.test_bn_bwd_bound_feeds_the_conv_backward(1e4)
+    TB.test_bn_bwd_bound_feeds_the_conv_backward(1e-6)
+
+
+@pytest.mark.parametrize('family', sorted(TR.FAMILIES))
+def test_engine2_family_off_unit_scale_kernels(family, monkeypatch):
+    """One magnitude triple per family on the host build (the GPU run has all four): the triple rotates over the families."""
+    mag = TR.MAGNITUDES[sorted(TR.FAMILIES).index(family) % len(TR.MAGNITUDES)]
+    TR.run_family(family, mag, monkeypatch)
+
+
+@pytest.mark.parametrize('family', sorted(TR.HOT))
+def test_engine2_one_hot_row_kernels(family):
+    TR.HOT[family]()
 
 
 def test_conv3_lds_image_is_conflict_free():
