@@ -615,6 +615,26 @@ int rih_adam_dev(const rih_adam_dev_entry* table, int ntensors, int64_t max_n, c
                  float beta2, float eps, void* stream);
 int rih_plateau_step(rih_opt_state* state, const float* loss, void* stream);
 
+/* Contact search of the pose optimiser's driver (pose_data_optimize/batch_optimize_mocap_origin.py: `search_anchors` :62-130 on
+ * the anchors and face normals of `update_scene` :260-270; csrc/rih_contact.hip, ABI 27; renderih_amd.contact_search).  One
+ * launch for B frames, one workgroup per frame, not differentiable.  verts_main / verts_sub[B][V][3]: the two hands' vertices,
+ * already translated; face_vert_idx[A][3] (range-checked against V by the HOST), weight[A][2], class_type[A].  Anchors by
+ * rih_anchor_fwd's expression; normals cross(v1 - v0, v2 - v0) normalised, the sub hand's negated (a degenerate face is
+ * outside the contract).  For sub anchor i and main anchor j, dis = |sub_i - main_j|.
+ *   prev_id == NULL (fresh search): dis counts as 1000 where n_sub_i . n_main_j > against_cos; anchor_id[b][i][0..D) = the D
+ *     smallest, EQUAL distances in ascending j; vertex_contact[b][i] = any dis < radius.
+ *   prev_id[B][A][D] (refresh): anchor_id = prev_id, the true distance to every previous id and no against rule;
+ *     vertex_contact = any of the row's D ids within the radius.  An id outside [0, A) is copied through with elastic 0 and
+ *     mask 0 and is not dereferenced.
+ *   elastic = (dis < radius) cos^2(pi dis / (2 radius)) (= 0.5 cos(pi dis / radius) + 0.5, but positive up to the radius in
+ *     fp32); mask = elastic > 0; elastic *= damp where class_type[i] != tip_class and class_type[id] != tip_class.
+ * Plain stores in a fixed order: two runs are bit-identical.
+ * RIH_EINVAL: a null pointer other than prev_id, B, V, A or D < 1, A > 1024, D > 8, D > A, a radius that is not positive. */
+int rih_contact_search(const float* verts_main, const float* verts_sub, const int32_t* face_vert_idx, const float* weight,
+                       const int32_t* class_type, const int64_t* prev_id, float radius, float against_cos, float damp,
+                       int tip_class, int64_t* anchor_id, float* elastic, int64_t* mask, int64_t* vertex_contact, int B, int V,
+                       int A, int D, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused mesh loss   (core/Loss.py:68-164 GraphLoss.calc_loss, :201-277 calc_loss_GCN; aux loss disabled there)
  * Constant topology of one hand (device pointers, uploaded once by the caller):
@@ -673,7 +693,7 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc, opt state, adam dev entry (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 26
+#define RIH_ABI_VERSION 27
 #define RIH_ABI_NSIZES 14
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);

@@ -227,6 +227,8 @@ SIGNATURES = {
     'rih_pose_prior_bwd': (c_i, [c_f, c_f, c_f, c_l, C.c_void_p]),
     'rih_adam_dev': (c_i, [C.c_void_p, c_i, c_l, C.c_void_p, c_fl, c_fl, c_fl, C.c_void_p]),
     'rih_plateau_step': (c_i, [C.c_void_p, c_f, C.c_void_p]),
+    'rih_contact_search': (c_i, [c_f, c_f, C.c_void_p, c_f, C.c_void_p, C.c_void_p, c_fl, c_fl, c_fl, c_i, C.c_void_p, c_f,
+                                 C.c_void_p, C.c_void_p, c_i, c_i, c_i, c_i, C.c_void_p]),
     'rih_mesh_loss': (c_i, [C.POINTER(MeshTopo), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_fl,
                             c_f, c_f, c_f, c_f, c_f, c_i, C.c_void_p]),
     'rih_mesh_loss_final': (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, C.c_void_p]),
@@ -253,7 +255,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 26     # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 27     # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 

@@ -29,8 +29,9 @@ DELIBERATE DEVIATIONS: the loss is summed as prior + 0.02 * lambda_repulsion * p
 penetration term before the ergonomics term: another rounding order).  The fused class hands the contact term elastic / mask.sum()
 and a mask sum of 1, so that the sum -- a launch argument of rih_pose_prior_fwd -- is not baked into the captured graph and
 another batch's contacts replay the same graph (one more rounding per contact pair; an empty mask still gives an exact 0).
-Not reproduced: NatureLoss (its weights are not in the checkout), the driver's numpy code (`update_scene`, `search_anchors`), the
-single-hand and object modes, progress bars; `n_iter` < 1 raises (the reference fails on its missing snapshot).
+The driver's numpy code (`update_scene`, `search_anchors`) and its attempt loop are renderih_amd.contact_search and
+renderih_amd.pose_driver.  Not reproduced: NatureLoss (its weights are not in the checkout), the single-hand and object modes,
+progress bars; `n_iter` < 1 raises (the reference fails on its missing snapshot).
 """
 import ctypes as C
 
