@@ -576,6 +576,39 @@ int rih_pose_prior_fwd(const float* q_r, const float* q_l, const float* verts_r,
 int rih_pose_prior_reduce(const float* partial, float lambda_contact, float* terms, float* loss, int B, void* stream);
 int rih_pose_prior_bwd(const float* grads, const float* grad_out, float* out, int64_t n, void* stream);
 
+/* The pose optimiser's NatureLoss: a pose discriminator's verdict on both hands as a loss (geo_optimizer_both_batch.py:110-132
+ * `GeOptimizer.NatureLoss`, added with weight 1 at :824; the network of Ver2Code/Discriminator/discrim.py:66-105;
+ * csrc/rih_nature.hip, ABI 28; renderih_amd.nature.FusedTwoHandNatureLoss).  fp32.  H = the network's hidden width, a multiple
+ * of 64 in [64, 512] (the reference's is 512).  Rows are the 2B hands, right hands first, then left.
+ * rih_nature_pack: the twelve tensors of the state dict in torch layout (w1[H][45], b1[H], w2..w4 and w_last [H][H] with their
+ *   biases [H], w_pred[2][H], b_pred[2]) -> packed (>= rih_nature_pack_floats(H) floats, 16-byte aligned): every weight once as
+ *   [in][out] for the forward and once as [out][in] for the backward, then the biases.  Once per loaded weight set.
+ * rih_nature_fwd (one workgroup of H threads per tile of rih_nature_tile_rows() rows): q_*[B][16][4] (w, x, y, z), NOT
+ *   normalised; the root is not read.  Per row: normalise, matrix with the conversion's own 2 / |q|^2, XYZ Euler angles
+ *   (atan2(-m12, m22), asin(m02), atan2(-m01, m00); asin's argument is CLAMPED to [-1, 1], the reference's is not), the six
+ *   layers, softmax (p0, p1), mask = p1 < 1.5 p0, bce = -(log(1 - p0) + log(p1)) / 2 with torch's log floor of -100.  ws
+ *   (>= rih_nature_ws_floats(B, H) floats, 16-byte aligned) receives the four activated layers [2B][4][H] and [2B][4] =
+ *   (p0, p1, bce, mask).
+ * rih_nature_reduce (one workgroup, fixed order): terms[4] = (mean bce of the masked right rows, of the masked left rows, the
+ *   two counts); a side without a masked row gives exactly 0; loss[0] = terms[0] + terms[1]; the per-row scale (1 / count of
+ *   its side, 0 for an unmasked row) goes into ws for the backward.  Nothing is read by the host.
+ * rih_nature_bwd (same tiles): dq_*[B][16][4] = grad_out[0] (DEVICE scalar) * d loss / d q_*, through the normalisation; the
+ *   root's gradient is written as 0; a clamped asin and a gimbal-locked atan2(0, 0) pass no gradient.  Every element of dq_* is
+ *   written, with plain stores: two runs are bit-identical.
+ * RIH_EINVAL: a null pointer, B < 1 or > RIH_NATURE_MAX_B, H not a multiple of 64 in [64, 512], packed or ws not 16-byte
+ * aligned; the two size queries return 0 for such B or H. */
+#define RIH_NATURE_MAX_B (1 << 20)
+int64_t rih_nature_pack_floats(int H);
+int64_t rih_nature_ws_floats(int B, int H);
+int rih_nature_tile_rows(void);
+int rih_nature_pack(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                    const float* w4, const float* b4, const float* w_last, const float* b_last, const float* w_pred,
+                    const float* b_pred, float* packed, int H, void* stream);
+int rih_nature_fwd(const float* packed, const float* q_r, const float* q_l, float* ws, int B, int H, void* stream);
+int rih_nature_reduce(float* ws, float* loss, float* terms, int B, int H, void* stream);
+int rih_nature_bwd(const float* packed, const float* q_r, const float* q_l, const float* ws, const float* grad_out, float* dq_r,
+                   float* dq_l, int B, int H, void* stream);
+
 /* Adam and the plateau scheduler of the pose optimiser with every scalar on the device (geo_optimizer_both_batch.py:428-432
  * `torch.optim.Adam` + `ReduceLROnPlateau`, :879-880 `optimizer.step(); scheduler.step(loss)`; csrc/rih_pose_opt.hip, ABI 25;
  * renderih_amd.pose_opt).  One optimiser iteration is rih_adam_dev then rih_plateau_step on the same stream, with no host read:
@@ -693,7 +726,7 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc, opt state, adam dev entry (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 27
+#define RIH_ABI_VERSION 28
 #define RIH_ABI_NSIZES 14
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);

@@ -225,6 +225,13 @@ SIGNATURES = {
                                  c_fl, c_fl, c_f, c_f, c_i, c_i, c_i, c_i, c_i, C.c_void_p]),
     'rih_pose_prior_reduce': (c_i, [c_f, c_fl, c_f, c_f, c_i, C.c_void_p]),
     'rih_pose_prior_bwd': (c_i, [c_f, c_f, c_f, c_l, C.c_void_p]),
+    'rih_nature_pack_floats': (c_l, [c_i]),
+    'rih_nature_ws_floats': (c_l, [c_i, c_i]),
+    'rih_nature_tile_rows': (c_i, []),
+    'rih_nature_pack': (c_i, [c_f] * 13 + [c_i, C.c_void_p]),
+    'rih_nature_fwd': (c_i, [c_f, c_f, c_f, c_f, c_i, c_i, C.c_void_p]),
+    'rih_nature_reduce': (c_i, [c_f, c_f, c_f, c_i, c_i, C.c_void_p]),
+    'rih_nature_bwd': (c_i, [c_f] * 7 + [c_i, c_i, C.c_void_p]),
     'rih_adam_dev': (c_i, [C.c_void_p, c_i, c_l, C.c_void_p, c_fl, c_fl, c_fl, C.c_void_p]),
     'rih_plateau_step': (c_i, [C.c_void_p, c_f, C.c_void_p]),
     'rih_contact_search': (c_i, [c_f, c_f, C.c_void_p, c_f, C.c_void_p, C.c_void_p, c_fl, c_fl, c_fl, c_i, C.c_void_p, c_f,
@@ -255,7 +262,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 27     # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 28     # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 

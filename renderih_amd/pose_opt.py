@@ -6,7 +6,11 @@ geo_optimizer_both_batch.py in mode='both': `set_opt_val(...)`, a mutable `coef_
 host-compiled kernels of the tests), `TwoHandPriorLoss`, `torch.optim.Adam` over the reference's four groups (translations of the right and the
 left hand at 0.01 lr, their 15 finger quaternions at lr) and `ReduceLROnPlateau(mode='min', factor=0.5, patience=20,
 min_lr=1e-5)`.  The objective is `loss_fn` :805-825 without the terms that are 0 in this mode:
-    quat_norm + edge + lambda_contact * contact + 0.02 * lambda_repulsion * penetration.mean() + ergonomics
+    quat_norm + edge + lambda_contact * contact + 0.02 * lambda_repulsion * penetration.mean() + ergonomics + 1 * nature
+`nature` is the reference's NatureLoss (renderih_amd.nature: `TwoHandNatureLoss` in the mirror, `FusedTwoHandNatureLoss` in the
+fused class), present only when the constructor is given `nature=` the discriminator's weights (the reference's
+Ver2Code/Discriminator/discrim.pth as a path, or a state dict).  With `nature=None`, the default, the term is absent: the same
+launches, the same graph and the same results as before the argument existed, and NOT the reference's objective.
 
 `FusedTwoHandPoseOptimizer` has the same surface on the fused modules.  One iteration -- both hands, anchors, penetration +
 prior, `torch.autograd.grad` to quaternions and translations, rih_adam_dev, rih_plateau_step (csrc/rih_pose_opt.hip) -- is
@@ -14,8 +18,9 @@ captured once per (batch shape, coef_val) in a `torch.cuda.graph` and replayed `
 loss and bad-epoch counter live in a device block (`DeviceAdamPlateau`), so `optimize()` reads the device only at its end.
 Changing `coef_val` or the batch shape recaptures, changing `n_iter` does not, and `set_opt_val` writes into the static
 buffers.  `graph=False` launches the same kernels without capture.  `last_loss` (0-dim) and `last_terms` (a dict: 'prior' the
-seven terms of `TwoHandPriorLoss`, 'penetration' [B]) are device tensors of the last iteration, in place of the reference's
-per-iteration `.item()` dictionary.
+seven terms of `TwoHandPriorLoss`, 'penetration' [B], and with weights 'nature' [4]: the two sides' means and their counts of
+judged rows) are device tensors of the last iteration, in place of the reference's per-iteration `.item()` dictionary.  The
+NatureLoss mask and its counts live on the device, so they are not part of the graph key.
 
 Quirks of the reference that both keep:
   * the shape (`hand_shape_init` [B,20], right then left) is never optimised: `optimize_hand_shape` is False on every path
@@ -26,12 +31,13 @@ Quirks of the reference that both keep:
   * the returned quaternions are not normalised.
   * `set_opt_val` creates fresh optimiser and scheduler state; a second `optimize()` without it continues.
 DELIBERATE DEVIATIONS: the loss is summed as prior + 0.02 * lambda_repulsion * penetration.mean() (the reference adds the
-penetration term before the ergonomics term: another rounding order).  The fused class hands the contact term elastic / mask.sum()
+penetration term before the ergonomics term: another rounding order), and the NatureLoss term is added last, as the
+reference does, each side's mean taken as renderih_amd.nature describes.  The fused class hands the contact term elastic / mask.sum()
 and a mask sum of 1, so that the sum -- a launch argument of rih_pose_prior_fwd -- is not baked into the captured graph and
 another batch's contacts replay the same graph (one more rounding per contact pair; an empty mask still gives an exact 0).
 The driver's numpy code (`update_scene`, `search_anchors`) and its attempt loop are renderih_amd.contact_search and
-renderih_amd.pose_driver.  Not reproduced: NatureLoss (its weights are not in the checkout), the single-hand and object modes,
-progress bars; `n_iter` < 1 raises (the reference fails on its missing snapshot).
+renderih_amd.pose_driver.  Not reproduced: the single-hand and object modes, progress bars; `n_iter` < 1 raises (the reference
+fails on its missing snapshot).
 """
 import ctypes as C
 
@@ -39,6 +45,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .nature import FusedTwoHandNatureLoss, TwoHandNatureLoss
 from .pose_prior import FusedTwoHandPriorLoss, TwoHandPriorLoss
 from .quat_mano import AnchorLayer, FusedAnchorLayer, FusedQuatManoLayer, QuatManoLayer
 from .sdf import FusedTwoHandSDFLoss, TwoHandSDFLoss, sdf
@@ -138,11 +145,13 @@ def _as(x, device, dtype):
 class TwoHandPoseOptimizer:
     """`GeOptimizer(mode='both')` in plain torch; see the module docstring.  `mano_right`, `mano_left`: model dicts or pickle
     paths as `QuatManoLayer` takes them; `anchor`: the anchor directory (or arrays) of `AnchorLayer`; `part_vert`, `faces`: the
-    hand-part table and the face list of `TwoHandSDFLoss` (faces=None: its default, the right hand's)."""
+    hand-part table and the face list of `TwoHandSDFLoss` (faces=None: its default, the right hand's); `nature`: the pose
+    discriminator's weights (a path or a state dict) for the NatureLoss term, None: no such term."""
     _classes = (QuatManoLayer, AnchorLayer, TwoHandSDFLoss, TwoHandPriorLoss)
+    _nature_class = TwoHandNatureLoss
 
     def __init__(self, mano_right, mano_left, anchor, part_vert, lr=1e-2, n_iter=2500, lambda_contact_loss=10.0,
-                 lambda_repulsion_loss=0.5, grid_size=32, faces=None, device='cpu', dtype=torch.float32):
+                 lambda_repulsion_loss=0.5, grid_size=32, faces=None, device='cpu', dtype=torch.float32, nature=None):
         mano_cls, anchor_cls, sdf_cls, prior_cls = self._classes
         self.device, self.dtype = torch.device(device), dtype
         self.lr, self.n_iter = float(lr), int(n_iter)
@@ -153,7 +162,8 @@ class TwoHandPoseOptimizer:
         self.prior = prior_cls(mano_right, mano_left, lambda_contact=lambda_contact_loss)
         if dtype != torch.float32:
             self.sdf_loss.sdf = _WidenedVoxeliser()
-        self.modules = self.hands + [self.anchor_layer, self.sdf_loss, self.prior]
+        self.nature = None if nature is None else self._nature_class(nature)
+        self.modules = self.hands + [self.anchor_layer, self.sdf_loss, self.prior] + ([] if nature is None else [self.nature])
         for m in self.modules:
             m.to(device=self.device, dtype=dtype) if dtype != torch.float32 else m.to(self.device)
         self.batch_size = None
@@ -206,12 +216,17 @@ class TwoHandPoseOptimizer:
 
     # ------------------------------------------------------------------ objective
     def _objective(self, q_r, q_l, t_r, t_l):
-        """-> loss, the prior's seven terms, the penetration loss per sample."""
+        """-> loss, the terms (the prior's seven, the penetration loss per sample, with weights NatureLoss's four)."""
         vr = self.hands[0](q_r, self.shape[:, :10])[0] + t_r.unsqueeze(1)
         vl = self.hands[1](q_l, self.shape[:, 10:])[0] + t_l.unsqueeze(1)
         pen = self.sdf_loss(torch.stack([vr, vl], 1))
         prior, terms = self.prior(q_r, q_l, vr, vl, self.anchor_layer(vr), self.anchor_layer(vl))
-        return prior + (REPULSION_SCALE * float(self.coef_val['lambda_repulsion_loss'])) * pen.mean(), terms, pen
+        loss = prior + (REPULSION_SCALE * float(self.coef_val['lambda_repulsion_loss'])) * pen.mean()
+        terms = {'prior': terms.detach(), 'penetration': pen.detach()}
+        if self.nature is not None:
+            nature, counts = self.nature(q_r, q_l)
+            loss, terms['nature'] = loss + 1.0 * nature, counts.detach()
+        return loss, terms
 
     def _ready(self):
         if self.batch_size is None:
@@ -229,12 +244,12 @@ class TwoHandPoseOptimizer:
         for _ in range(int(self.n_iter)):
             self.optimizer.zero_grad()
             q = [torch.cat([r, v], 1) for r, v in zip(self.roots, self.var)]           # the reference's assembled copies
-            loss, terms, pen = self._objective(q[0], q[1], self.tsl[0], self.tsl[1])
+            loss, terms = self._objective(q[0], q[1], self.tsl[0], self.tsl[1])
             loss.backward()
             self.optimizer.step()
             self.scheduler.step(loss.detach())
             self.snapshot = [x.detach() for x in q]
-            self.last_loss, self.last_terms = loss.detach(), {'prior': terms.detach(), 'penetration': pen.detach()}
+            self.last_loss, self.last_terms = loss.detach(), terms
         return self._result(self.snapshot)
 
 
@@ -242,6 +257,7 @@ class TwoHandPoseOptimizer:
 class FusedTwoHandPoseOptimizer(TwoHandPoseOptimizer):
     """`TwoHandPoseOptimizer` on the HIP kernels, one iteration = one replayed graph; see the module docstring.  GPU fp32 only."""
     _classes = (FusedQuatManoLayer, FusedAnchorLayer, FusedTwoHandSDFLoss, FusedTwoHandPriorLoss)
+    _nature_class = FusedTwoHandNatureLoss
     _CONTACT_CONSTANTS = ('anchor_id', 'elastic', 'cptr', 'clist')
 
     def __init__(self, *args, graph=True, device='cuda', **kwargs):
@@ -301,13 +317,13 @@ class FusedTwoHandPoseOptimizer(TwoHandPoseOptimizer):
         self.batch_size = B
 
     def _iteration(self):
-        loss, terms, pen = self._objective(self.q[0], self.q[1], self.tsl[0], self.tsl[1])
+        loss, terms = self._objective(self.q[0], self.q[1], self.tsl[0], self.tsl[1])
         grads = [g if g.is_contiguous() else g.contiguous() for g in torch.autograd.grad(loss, self.tsl + self.q)]
         if not self._capturing:                                     # under capture the table is filled afterwards
             self.stepper.set_grads(grads)
         self.stepper.step(loss)
         self._grads = grads                                         # the launch table points at them
-        self.last_loss, self.last_terms = loss.detach(), {'prior': terms, 'penetration': pen.detach()}
+        self.last_loss, self.last_terms = loss.detach(), terms
 
     def _capture(self, key):
         """Warm up on a side stream (on copies of the state: the warm-up iteration is undone), capture one iteration, then

@@ -31,8 +31,8 @@ tensor.  Here mask, anchor_id and elastic are constants given to `set_contacts`,
 an empty mask gives an exact scalar 0 with zero gradients; `forward` never reads device memory.  The orientation of an edge
 row is (smaller, larger) index; the reference's is the iteration order of a two-element Python set (the loss is symmetric).
 `terms` of the fused class carries no gradient (the mirror's does).
-Not reproduced: NatureLoss (its weights are not in the checkout), the terms loss_fn multiplies by 0 or has commented out, the
-single-hand / object mode.  The Adam + ReduceLROnPlateau loop around this loss: renderih_amd/pose_opt.py.
+Not reproduced: the terms loss_fn multiplies by 0 or has commented out, the single-hand / object mode.  NatureLoss is
+renderih_amd/nature.py.  The Adam + ReduceLROnPlateau loop around this loss: renderih_amd/pose_opt.py.
 """
 import math
 
