@@ -678,7 +678,11 @@ class EmulatedLib:
 
     def rih_flash_attention_fwd(self, q, q_ld, k, v, kv_ld, B, heads, Sq, Sk, d, alpha, drop_p, seed, seed_dev, out, ld_out,
                                 lse, stream):
-        assert d in (16, 32, 64) and B * heads <= 65535
+        # the refusals of the entry point, before anything is read or written
+        if not (q and k and v and out and lse) or B < 1 or heads < 1 or Sq < 1 or Sk < 1 or d not in (16, 32, 64):
+            return -1
+        if q_ld < d or kv_ld < d or ld_out < heads * d or not 0.0 <= drop_p < 1.0 or B * heads > 65535:
+            return -1
         seed = self._seed(seed, seed_dev)
         Q = _f(q, (B * Sq - 1) * q_ld + heads * d)
         Kk = _f(k, (B * Sk - 1) * kv_ld + heads * d)
@@ -697,6 +701,11 @@ class EmulatedLib:
 
     def rih_flash_attention_bwd(self, dO, do_ld, O, o_ld, q, q_ld, k, v, kv_ld, B, heads, Sq, Sk, d, alpha, drop_p, seed,
                                 seed_dev, lse, Dws, dq, dq_ld, dk, dv, dkv_ld, stream):
+        if not (dO and O and q and k and v and lse and Dws and dq and dk and dv) or B < 1 or heads < 1 or Sq < 1 or Sk < 1:
+            return -1
+        if (d not in (16, 32, 64) or q_ld < d or kv_ld < d or do_ld < heads * d or o_ld < heads * d or dq_ld < d or dkv_ld < d
+                or not 0.0 <= drop_p < 1.0 or B * heads > 65535):
+            return -1
         seed = self._seed(seed, seed_dev)
         G = _f(dO, (B * Sq - 1) * do_ld + heads * d)
         Om = _f(O, (B * Sq - 1) * o_ld + heads * d)

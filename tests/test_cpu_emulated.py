@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import test_gpu_flash_edges as TF
 import test_gpu_ops as G
 import test_gpu_rows_tiles as TRT
 from abi_emulator import emulated_abi
@@ -16,6 +17,7 @@ from renderih_amd.testing import assert_close
 def _emulate(monkeypatch):
     monkeypatch.setattr(G, 'dev', lambda: torch.device('cpu'))
     monkeypatch.setattr(TRT, 'dev', lambda: torch.device('cpu'))
+    monkeypatch.setattr(TF, 'dev', lambda: torch.device('cpu'))
     with emulated_abi():
         yield
 
@@ -43,6 +45,15 @@ def test_other_ops_host_logic():
     G.test_cross_attention_packed(2, 63, 256, 4)
     G.test_add_dropout_and_bcast()
     G.test_cheby_gather_project()
+
+
+def test_flash_entry_points_of_the_emulator_refuse_and_return_lse():
+    """The numpy restatement of rih_flash_attention_* keeps the contract the kernels are tested for in
+    tests/test_gpu_flash_edges.py: the same refusals (RIH_EINVAL, outputs untouched) and the lse word, here on pitched operands
+    one float off alignment."""
+    TF.check_refusals()
+    TF.check_lse_word((1, 33, 31, 64, 4), 'qk30')
+    TF.check_unaligned_bit_identical((1, 33, 31, 64, 4), 0.25, 97531)
 
 
 def test_paired_layers_host_logic():

@@ -761,7 +761,9 @@ def test_flash_attention_equals_three_kernel_path(B, Sq, Sk, D, h, p):
     try:
         for flash in (False, True):
             ops.FLASH_ATTN = flash
-            tg = [t.to(d).requires_grad_(True) for t in (q, k, v)]
+            # (fresh leaves per path: where dev() is the CPU, .to() alone returns q, k, v themselves and both paths would add
+            # into the same .grad tensors, which the comparison below would then hold against themselves)
+            tg = [t.clone().to(d).requires_grad_(True) for t in (q, k, v)]
             y = ops.attention(tg[0], tg[1], tg[2], h, p, 987654321)
             y.backward(gy.to(d))
             res.append([y.detach()] + [t.grad for t in tg])

@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.join(HERE, 'hipcpu'))
 
 import test_gpu_bounds as TB        # noqa: E402
 import test_gpu_e2_range as TR      # noqa: E402
+import test_gpu_flash_edges as TF    # noqa: E402
 import test_gpu_loss as TL          # noqa: E402
 import test_gpu_mano as TMANO       # noqa: E402
 import test_gpu_ops as G            # noqa: E402
@@ -29,7 +30,7 @@ CPU = torch.device('cpu')
 @pytest.fixture(autouse=True)
 def _host_kernels(monkeypatch):
     from host_kernels import host_kernels_abi
-    for mod in (G, TB, TR, TL, TMANO, TRT):
+    for mod in (G, TB, TR, TL, TMANO, TRT, TF):
         monkeypatch.setattr(mod, 'dev', lambda: CPU)
     with host_kernels_abi():
         yield
@@ -342,6 +343,27 @@ def test_linear_dropout_epilogue_kernels(case):
 @pytest.mark.parametrize('case', [(2, 40, 40, 256, 4, 0.0), (1, 70, 33, 128, 4, 0.1), (1, 33, 130, 64, 4, 0.05), (2, 1, 5, 32, 2, 0.0)])
 def test_flash_attention_kernels(case):
     G.test_flash_attention_equals_three_kernel_path(*case)
+
+
+def test_flash_edges_on_cpu():
+    """tests/test_gpu_flash_edges.py on the host build of csrc/rih_flash.hip: the fp64 bar at every shape x scales 1 and 30, the
+    orderings of the running maximum (and the forward at the full lift), the lse word, the unaligned launch and the refusals."""
+    FC = TF.FC
+    for case in FC.CASES:
+        if case[1] in ('qk1', 'qk30') + tuple(FC.ORDERINGS):
+            TF.check_vs_fp64(*case)
+    for case in FC.THREE_KERNEL_CASES[:2]:
+        TF.check_vs_fp64(*case, flash=False)
+    for case in TF.LSE_CASES:
+        TF.check_lse_word(*case)
+    for case in FC.FWD_CASES:
+        TF.check_forward_at_full_lift(*case)
+    TF.check_unaligned_bit_identical((1, 33, 31, 64, 4))
+    TF.check_unaligned_bit_identical((1, 129, 33, 256, 4))
+    TF.check_unaligned_bit_identical((1, 33, 31, 64, 4), 0.25, 97531)
+    TF.check_dropout((1, 129, 33, 64, 4))
+    TF.check_entry_points(33, 0.25)
+    TF.check_refusals()
 
 
 def test_graph_and_resampling_kernels():
