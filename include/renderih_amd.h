@@ -188,7 +188,11 @@ int rih_splitk_reduce_bias(const float* P, int S, int Mp, int M, int N, float* d
 /* Any number of independent reductions (each as rih_splitk_reduce_bias) in ceil(n/56) launches: the split-K partials of
  * the weight gradients of a whole backward stage are summed at the END of the stage instead of one small launch behind
  * every weight-gradient GEMM (157 launches of ~8 us per ResNet50 step; a dependent kernel costs >= 4.5 us on this
- * platform whatever its size).  `descs` is HOST memory, read before the call returns.  Same fixed summation order. */
+ * platform whatever its size).  `descs` is HOST memory, read before the call returns.  Same fixed summation order.
+ * Two kernels, one result (bitwise): reductions with N % 4 == 0, 16-byte aligned P, M == taps * Cin, CinValid <= Cin and
+ * taps <= 96 -- in rih_splitk_reduce_bias(_batched) too (batched: sP % 4 == 0) -- run on 16-byte loads and, below S = 32, write
+ * runs of taps * (ci range) floats per n through LDS (from S = 32: the four partial sums of an element on four lanes, stores as
+ * the reference); the others run on the reference kernel (one element per thread). */
 typedef struct rih_reduce_desc {
     const float* P;         /* [S][Mp][N] partial slabs */
     float* dst;             /* parameter-layout gradient, see rih_splitk_reduce */
@@ -196,7 +200,7 @@ typedef struct rih_reduce_desc {
     int32_t S, Mp, M, N, Cin, taps, CinValid, accumulate;
     int32_t CinPitch;       /* 0: dst is the whole parameter [N][CinValid][taps]; > 0: dst points at the first of CinValid columns of a
                                wider parameter [N][CinPitch][taps] (the column slice of one part of a concatenated input, a_seg) */
-    int32_t reserved;
+    int32_t reserved;       /* 0; != 0 keeps this reduction on the reference kernel (below) */
 } rih_reduce_desc;
 int rih_splitk_reduce_multi(const rih_reduce_desc* descs, int n, void* stream);
 /* nb independent reductions in one launch: slice b reads P + b*sP and writes dst + b*sDst, db + b*sDb (the split-K
@@ -248,8 +252,11 @@ typedef struct rih_h2_desc {
     void* dst;              /* [N][Kpad / 8][2][8] fp16: N = Cout (for_dgrad 0) or CinPad (1), Kpad >= KH*KW*CinPad (resp. *Cout), % 32 */
     const float* amax;      /* bound block of w */
     int32_t Cout, Cin, KH, KW, CinPad, for_dgrad, Kpad;
+    int32_t reserved;       /* 0; != 0: the gathering reference kernel (below).  Takes the struct's former tail padding: same size */
 } rih_h2_desc;
-/* any number of H2 weight operands in ceil(n / 48) launches (`descs` is HOST memory, read before the call returns) */
+/* any number of H2 weight operands in ceil(n / 48) launches (`descs` is HOST memory, read before the call returns).  Operands with
+ * KH * KW <= 127 and (forward: CinPad % 8 == 0, or CinPad * KH * KW < 4096 as for the stem; data gradient: Cout % 8 == 0) are read
+ * coalesced through an LDS tile; the others, and descriptors with reserved != 0, by the gathering kernel.  Same bits either way. */
 int rih_h2_multi(const rih_h2_desc* descs, int n, void* stream);
 
 /* Short-reduction streaming GEMM (csrc/rih_conv3.hip `panel_kernel`, ABI 16): C[M][N] = act(A[M][K] W[N][K]^T (+ R)) for the 1x1
@@ -313,7 +320,9 @@ int rih_pack_conv_weight(const float* w, float* dst, int Cout, int Cin, int KH, 
 typedef struct rih_pack_desc {
     const float* w;         /* OIHW parameter */
     float* dst;
-    int32_t Cout, Cin, KH, KW, CinPad, mode, kh0, kw0, step, Th, Tw, reserved;
+    int32_t Cout, Cin, KH, KW, CinPad, mode, kh0, kw0, step, Th, Tw;
+    int32_t reserved;       /* 0; != 0 keeps this operand on the reference kernel (one element per thread) instead of the tiled
+                               transpose through LDS that operands with KH * KW <= 63 take.  Same bits either way. */
 } rih_pack_desc;
 int rih_pack_conv_weight_multi(const rih_pack_desc* descs, int n, void* stream);
 /* Tap subset for one parity class of a strided data gradient:

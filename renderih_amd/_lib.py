@@ -53,7 +53,7 @@ class PanelDesc(C.Structure):
 
 class H2Desc(C.Structure):
     _fields_ = [('w', C.c_void_p), ('dst', C.c_void_p), ('amax', C.c_void_p)] + \
-               [(n, C.c_int32) for n in ('Cout', 'Cin', 'KH', 'KW', 'CinPad', 'for_dgrad', 'Kpad')]
+               [(n, C.c_int32) for n in ('Cout', 'Cin', 'KH', 'KW', 'CinPad', 'for_dgrad', 'Kpad', 'reserved')]
 
 
 class AbsmaxDesc(C.Structure):

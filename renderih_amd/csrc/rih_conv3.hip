@@ -324,6 +324,7 @@ struct H2WArgs {
     const float* amax;
     int N, K, Kp, for_dgrad;
     int Cout, Cin, KH, KW, CinPad;
+    int wide;       // the launcher's choice: 1 = h2w_wide_block, 0 = h2w_span
 };
 __device__ __forceinline__ float h2w_fetch(const H2WArgs& a, int n, int k) {
     if (k >= a.K) return 0.f;
@@ -352,6 +353,109 @@ __device__ __forceinline__ void h2w_span(const H2WArgs& a, long long first, long
         d[1] = l;
     }
 }
+// The same planes with coalesced reads ("wide" path): h2w_fetch gathers a thread's 8 k at a stride of taps floats (forward) or
+// Cin * taps floats (data gradient).  Here a block stages the weights of a (co range) x (ci range) x all taps tile -- for each co
+// one contiguous span of the OIHW parameter -- into LDS as T[co][ci * taps + tap], and every thread builds its 8-k groups from
+// there: same scale, same e2_split2h on the same values, so the same bits.  Forward: a group is 8 ci of one tap (CinPad % 8 == 0);
+// where groups straddle taps (the stem: CinPad 4) the tile holds the whole K of its rows.  Data gradient: a group is 8 co of one
+// flipped tap (Cout % 8 == 0).  The k >= K padding groups go to the tiles with ci0 == 0 (forward) resp. co0 == 0.
+constexpr int H2W_LDS = 4096;           // floats
+struct H2Tile { int cob, cib, lp, ok; };
+__host__ __device__ inline H2Tile h2w_tile(const H2WArgs& a) {
+    H2Tile t;
+    t.cob = t.cib = t.lp = t.ok = 0;
+    const long long taps = (long long)a.KH * a.KW;
+    if (taps > 127) return t;
+    if (!a.for_dgrad) {
+        if (a.CinPad % 8 == 0) t.cib = taps == 1 ? 64 : 32;
+        else if (a.CinPad * taps < H2W_LDS) t.cib = a.CinPad;
+        else return t;
+        t.lp = (t.cib * (int)taps) | 1;
+        if (t.lp > H2W_LDS) return t;
+        t.cob = H2W_LDS / t.lp > 64 ? 64 : H2W_LDS / t.lp;
+    } else {
+        if (a.Cout % 8 != 0) return t;
+        t.cob = 32;
+        t.cib = 127 / (int)taps > 64 ? 64 : 127 / (int)taps;
+        t.lp = (t.cib * (int)taps) | 1;
+    }
+    t.ok = 1;
+    return t;
+}
+inline long long h2w_wide_tiles(const H2WArgs& a, const H2Tile& t) {
+    return (long long)((a.Cout + t.cob - 1) / t.cob) * ((a.CinPad + t.cib - 1) / t.cib);
+}
+__device__ __forceinline__ void h2w_store(const H2WArgs& a, int n, int g, const float* v, float sc) {
+    uint4 h, l;
+    e2_split2h(v[0], v[1], sc, h.x, l.x);
+    e2_split2h(v[2], v[3], sc, h.y, l.y);
+    e2_split2h(v[4], v[5], sc, h.z, l.z);
+    e2_split2h(v[6], v[7], sc, h.w, l.w);
+    uint4* d = reinterpret_cast<uint4*>(a.dst + ((long long)n * (a.Kp / 8) + g) * 32);
+    d[0] = h;
+    d[1] = l;
+}
+__device__ __forceinline__ void h2w_wide_block(const H2WArgs& a, int bx) {
+    __shared__ float T[H2W_LDS];
+    const H2Tile t = h2w_tile(a);
+    const int taps = a.KH * a.KW, G = a.Kp / 8, lp = t.lp;
+    const int tilesCi = (a.CinPad + t.cib - 1) / t.cib;
+    const int co0 = (bx / tilesCi) * t.cob, ci0 = (bx % tilesCi) * t.cib;
+    const int cobv = a.Cout - co0 < t.cob ? a.Cout - co0 : t.cob;
+    const int cibv = a.CinPad - ci0 < t.cib ? a.CinPad - ci0 : t.cib;
+    const int span = cibv * taps;
+    const int live = a.Cin - ci0 < cibv ? (a.Cin - ci0 > 0 ? (a.Cin - ci0) * taps : 0) : span;       // the rest are zero rows
+#pragma unroll 4
+    for (int c = threadIdx.x >> 6; c < cobv; c += 4) {       // a wavefront per co: one contiguous span of the parameter
+        const long long src = ((long long)(co0 + c) * a.Cin + ci0) * taps;
+        for (int e = threadIdx.x & 63; e < span; e += 64) T[c * lp + e] = e < live ? a.w[src + e] : 0.f;
+    }
+    __syncthreads();
+    const float sc = e2_scale(a.amax);
+    float v[8];
+    if (!a.for_dgrad && a.CinPad % 8 != 0) {            // whole rows: any group, k = (tap, ci) element by element
+        for (int i = threadIdx.x; i < cobv * G; i += 256) {
+            const int c = i / G, g = i - c * G;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int k = 8 * g + j, tap = k / a.CinPad, ci = k - tap * a.CinPad;
+                v[j] = k < a.K ? T[c * lp + ci * taps + tap] : 0.f;
+            }
+            h2w_store(a, co0 + c, g, v, sc);
+        }
+        return;
+    }
+    const int g_pad = a.K / 8;                          // K % 8 == 0 on both remaining forms
+    if (!a.for_dgrad) {
+        const int gpt = cibv / 8, per = taps * gpt;     // groups per tap, per row
+        for (int i = threadIdx.x; i < cobv * per; i += 256) {
+            const int c = i / per, r = i - c * per;
+            const int tap = r / gpt, q = r - tap * gpt;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = T[c * lp + (8 * q + j) * taps + tap];
+            h2w_store(a, co0 + c, (tap * a.CinPad + ci0) / 8 + q, v, sc);
+        }
+        if (ci0 != 0) return;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = 0.f;
+        for (int i = threadIdx.x; i < cobv * (G - g_pad); i += 256)
+            h2w_store(a, co0 + i / (G - g_pad), g_pad + i % (G - g_pad), v, sc);
+    } else {
+        const int gpc = cobv / 8, per = taps * gpc;     // groups per tap, per row (n = ci)
+        for (int i = threadIdx.x; i < cibv * per; i += 256) {
+            const int cl = i / per, r = i - cl * per;
+            const int tt = r / gpc, q = r - tt * gpc;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = T[(8 * q + j) * lp + cl * taps + (taps - 1 - tt)];
+            h2w_store(a, ci0 + cl, (tt * a.Cout + co0) / 8 + q, v, sc);
+        }
+        if (co0 != 0) return;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = 0.f;
+        for (int i = threadIdx.x; i < cibv * (G - g_pad); i += 256)
+            h2w_store(a, ci0 + i / (G - g_pad), g_pad + i % (G - g_pad), v, sc);
+    }
+}
 constexpr int H2_PACK = 48;
 struct H2Pack {
     H2WArgs d[H2_PACK];
@@ -364,7 +468,8 @@ __global__ __launch_bounds__(256) void h2_weight_multi_kernel(const H2Pack pk) {
     int k = 0;
     while (k + 1 < pk.n && b >= pk.first[k + 1]) ++k;
     const int nb = pk.first[k + 1] - pk.first[k];
-    h2w_span(pk.d[k], (long long)(b - pk.first[k]) * 256 + threadIdx.x, (long long)nb * 256);
+    if (pk.d[k].wide) h2w_wide_block(pk.d[k], b - pk.first[k]);
+    else h2w_span(pk.d[k], (long long)(b - pk.first[k]) * 256 + threadIdx.x, (long long)nb * 256);
 }
 
 int h2_args(H2WArgs& a, const rih_h2_desc& d) {
@@ -375,6 +480,7 @@ int h2_args(H2WArgs& a, const rih_h2_desc& d) {
     a.Cout = d.Cout; a.Cin = d.Cin; a.KH = d.KH; a.KW = d.KW; a.CinPad = d.CinPad;
     if (!a.for_dgrad) { a.N = d.Cout; a.K = d.KH * d.KW * d.CinPad; }
     else { a.N = d.CinPad; a.K = d.KH * d.KW * d.Cout; }
+    a.wide = (d.reserved == 0 && h2w_tile(a).ok) ? 1 : 0;       // rih_h2_desc.reserved != 0: the reference path
     return a.Kp < a.K ? RIH_EINVAL : RIH_OK;
 }
 
@@ -1107,6 +1213,8 @@ extern "C" int rih_h2_multi(const rih_h2_desc* descs, int n, void* stream) {
             const long long units = (long long)pk.d[i].N * (pk.d[i].Kp / 8);
             long long nb = (units + 255) / 256;
             if (nb > 512) nb = 512;
+            if (pk.d[i].wide) nb = h2w_wide_tiles(pk.d[i], h2w_tile(pk.d[i]));
+            if (total + nb > 0x7fffffffLL) return RIH_EINVAL;
             pk.first[i] = total;
             total += (int)nb;
         }

@@ -1247,15 +1247,206 @@ __device__ __forceinline__ void splitk_reduce_block(const float* __restrict__ P,
     }
 }
 
+// The same reduction at memory speed ("wide" path) for N % 4 == 0 and 16-byte aligned slabs -- the trunk's weight gradients,
+// whose slabs are tens of MB per convolution at S = 3..16, where one 4-byte load per slab and thread and a 4-byte store every
+// taps floats ran at a third of the copy rate.  A thread owns four consecutive n (one 16-byte load per slab) of one or two
+// slab rows; a block owns 32 n and ALL taps of a range of ci (reduce_wide_ci), so that through LDS it writes, for each n, one run of
+// taps * (ci range) consecutive floats of the parameter layout.  Per element the summation order is that of
+// splitk_reduce_block (a_j takes k = j mod 4 in increasing k, the tail goes into a0, (a0 + a1) + (a2 + a3)): same bits.
+constexpr int RW_NT = 32;           // n per tile
+constexpr int RW_ROWS = 96;         // most slab rows (tap, ci) per tile
+constexpr int RW_LP = RW_ROWS + 1;  // LDS pitch of one n: 4 * nq * 97 + e hits 32 different banks per half wave
+__host__ __device__ inline int reduce_wide_ci(int taps) {       // ci per tile: <= 64 rows (two per thread, one round), else <= RW_ROWS
+    if (taps == 1) return 64;
+    return taps > 64 ? 1 : 64 / taps;
+}
+#define RIH_RW_ADD(A, V) { A.x += V.x; A.y += V.y; A.z += V.z; A.w += V.w; }
+#define RIH_RW_LD(Q, K) (*reinterpret_cast<const float4*>((Q) + (long long)(K) * slab))
+#define RIH_RW_FIN(R, A0, A1, A2, A3)                                                                                  \
+    { R.x = (A0.x + A1.x) + (A2.x + A3.x); R.y = (A0.y + A1.y) + (A2.y + A3.y);                                        \
+      R.z = (A0.z + A1.z) + (A2.z + A3.z); R.w = (A0.w + A1.w) + (A2.w + A3.w); }
+__device__ __forceinline__ float4 reduce_wide_row(const float* __restrict__ q, int S, long long slab) {
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 a0 = z, a1 = z, a2 = z, a3 = z;
+    int k = 0;
+    for (; k + 7 < S; k += 8) {         // eight loads in flight; the adds in the order of the four-wide loop
+        const float4 v0 = RIH_RW_LD(q, k), v1 = RIH_RW_LD(q, k + 1), v2 = RIH_RW_LD(q, k + 2), v3 = RIH_RW_LD(q, k + 3);
+        const float4 v4 = RIH_RW_LD(q, k + 4), v5 = RIH_RW_LD(q, k + 5), v6 = RIH_RW_LD(q, k + 6), v7 = RIH_RW_LD(q, k + 7);
+        RIH_RW_ADD(a0, v0) RIH_RW_ADD(a1, v1) RIH_RW_ADD(a2, v2) RIH_RW_ADD(a3, v3)
+        RIH_RW_ADD(a0, v4) RIH_RW_ADD(a1, v5) RIH_RW_ADD(a2, v6) RIH_RW_ADD(a3, v7)
+    }
+    for (; k + 3 < S; k += 4) {
+        const float4 v0 = RIH_RW_LD(q, k), v1 = RIH_RW_LD(q, k + 1), v2 = RIH_RW_LD(q, k + 2), v3 = RIH_RW_LD(q, k + 3);
+        RIH_RW_ADD(a0, v0) RIH_RW_ADD(a1, v1) RIH_RW_ADD(a2, v2) RIH_RW_ADD(a3, v3)
+    }
+    for (; k < S; ++k) { const float4 v = RIH_RW_LD(q, k); RIH_RW_ADD(a0, v) }
+    float4 r;
+    RIH_RW_FIN(r, a0, a1, a2, a3)
+    return r;
+}
+// two rows at once: for S >= 4 eight 16-byte loads are issued before the first add, at S = 3 six
+__device__ __forceinline__ void reduce_wide_row2(const float* __restrict__ qa, const float* __restrict__ qb, int S,
+                                                 long long slab, float4& ra, float4& rb) {
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 a0 = z, a1 = z, a2 = z, a3 = z, b0 = z, b1 = z, b2 = z, b3 = z;
+    int k = 0;
+    for (; k + 3 < S; k += 4) {
+        const float4 v0 = RIH_RW_LD(qa, k), v1 = RIH_RW_LD(qa, k + 1), v2 = RIH_RW_LD(qa, k + 2), v3 = RIH_RW_LD(qa, k + 3);
+        const float4 w0 = RIH_RW_LD(qb, k), w1 = RIH_RW_LD(qb, k + 1), w2 = RIH_RW_LD(qb, k + 2), w3 = RIH_RW_LD(qb, k + 3);
+        RIH_RW_ADD(a0, v0) RIH_RW_ADD(a1, v1) RIH_RW_ADD(a2, v2) RIH_RW_ADD(a3, v3)
+        RIH_RW_ADD(b0, w0) RIH_RW_ADD(b1, w1) RIH_RW_ADD(b2, w2) RIH_RW_ADD(b3, w3)
+    }
+    const int t = S - k;                // 0..3 tail slabs, into a0 / b0 in order
+    if (t > 0) {
+        const float4 v0 = RIH_RW_LD(qa, k), w0 = RIH_RW_LD(qb, k);
+        const float4 v1 = RIH_RW_LD(qa, t > 1 ? k + 1 : k), w1 = RIH_RW_LD(qb, t > 1 ? k + 1 : k);
+        const float4 v2 = RIH_RW_LD(qa, t > 2 ? k + 2 : k), w2 = RIH_RW_LD(qb, t > 2 ? k + 2 : k);
+        RIH_RW_ADD(a0, v0) RIH_RW_ADD(b0, w0)
+        if (t > 1) { RIH_RW_ADD(a0, v1) RIH_RW_ADD(b0, w1) }
+        if (t > 2) { RIH_RW_ADD(a0, v2) RIH_RW_ADD(b0, w2) }
+    }
+    RIH_RW_FIN(ra, a0, a1, a2, a3)
+    RIH_RW_FIN(rb, b0, b1, b2, b3)
+}
+__device__ __forceinline__ void splitk_reduce_wide_block(const float* __restrict__ P, int S, int Mp, int M, int N,
+                                                         float* __restrict__ dst, int Cin, int taps, int CinValid,
+                                                         int accumulate, float* __restrict__ db, int ntiles, int bx,
+                                                         int CinPitch) {
+    if (bx >= ntiles) {     // the bias row: the blocks and the order of splitk_reduce_block (ntiles only moves them)
+        splitk_reduce_block(P, S, Mp, M, N, dst, Cin, taps, CinValid, accumulate, db, 0, bx - ntiles, CinPitch);
+        return;
+    }
+    __shared__ float wtile[RW_NT * RW_LP];
+    const int pitch = CinPitch > 0 ? CinPitch : CinValid;
+    const long long slab = (long long)Mp * N;
+    const int cr = reduce_wide_ci(taps);
+    const int tilesN = (N + RW_NT - 1) / RW_NT;
+    const int c0 = (bx / tilesN) * cr, n0 = (bx % tilesN) * RW_NT;
+    const int crv = CinValid - c0 < cr ? CinValid - c0 : cr;
+    const int rows = crv * taps;        // row e of the tile = (ci - c0) * taps + tap: the order of the parameter layout
+    {
+        const int nq = threadIdx.x & 7, n = n0 + 4 * nq;
+        if (n < N) {                    // N % 4 == 0: the whole quad is inside
+            float* t = wtile + 4 * nq * RW_LP;
+            for (int e = threadIdx.x >> 3; e < rows; e += 64) {
+                const int cj = e / taps, tap = e - cj * taps;
+                const float* qa = P + ((long long)tap * Cin + c0 + cj) * N + n;
+                float4 ra, rb;
+                if (e + 32 < rows) {
+                    const int cj2 = (e + 32) / taps, tap2 = e + 32 - cj2 * taps;
+                    reduce_wide_row2(qa, P + ((long long)tap2 * Cin + c0 + cj2) * N + n, S, slab, ra, rb);
+                    t[e + 32] = rb.x; t[RW_LP + e + 32] = rb.y; t[2 * RW_LP + e + 32] = rb.z; t[3 * RW_LP + e + 32] = rb.w;
+                } else {
+                    ra = reduce_wide_row(qa, S, slab);
+                }
+                t[e] = ra.x; t[RW_LP + e] = ra.y; t[2 * RW_LP + e] = ra.z; t[3 * RW_LP + e] = ra.w;
+            }
+        }
+    }
+    __syncthreads();
+    const int total = RW_NT * rows;
+    for (int i = threadIdx.x; i < total; i += 256) {
+        const int nl = i / rows, e = i - nl * rows;
+        if (n0 + nl < N) {
+            const long long o = ((long long)(n0 + nl) * pitch + c0) * taps + e;
+            const float v = wtile[nl * RW_LP + e];
+            dst[o] = accumulate ? dst[o] + v : v;
+        }
+    }
+}
+// S >= RW_DEEP ("deep" form of the wide path): few outputs under many slabs -- layer1 and the stem at S = 128..256, the decoder --
+// where a block of the form above would stream megabytes alone.  The tiles of splitk_reduce_block (8 m x 32 n, one block per 256
+// outputs; the stores are S times rarer than the loads, so they stay as there), a thread again four n wide, and the four chains
+// a_0..a_3 of an element on four lanes of a wavefront, eight 16-byte loads deep each; the lanes exchange the chains by shuffles
+// and form (a0 + a1) + (a2 + a3): float addition commutes, so whichever lane of a pair adds, the bits are those of the contract.
+constexpr int RW_DEEP = 32;
+__device__ __forceinline__ float4 reduce_shfl_add(const float4& a, int mask) {
+    float4 r;
+    r.x = a.x + __shfl_xor(a.x, mask, 64); r.y = a.y + __shfl_xor(a.y, mask, 64);
+    r.z = a.z + __shfl_xor(a.z, mask, 64); r.w = a.w + __shfl_xor(a.w, mask, 64);
+    return r;
+}
+__device__ __forceinline__ void splitk_reduce_deep_block(const float* __restrict__ P, int S, int Mp, int M, int N,
+                                                         float* __restrict__ dst, int Cin, int taps, int CinValid,
+                                                         int accumulate, float* __restrict__ db, int ntiles, int bx,
+                                                         int CinPitch) {
+    if (bx >= ntiles) {
+        splitk_reduce_block(P, S, Mp, M, N, dst, Cin, taps, CinValid, accumulate, db, 0, bx - ntiles, CinPitch);
+        return;
+    }
+    __shared__ float dtile[8][33];
+    const int pitch = CinPitch > 0 ? CinPitch : CinValid;
+    const long long slab = (long long)Mp * N;
+    const int nq = threadIdx.x & 7, j = (threadIdx.x >> 3) & 3, rl = threadIdx.x >> 5;     // j: lane bits 3..4
+    const int tilesN = (N + 31) / 32;
+    const int m0 = (bx / tilesN) * 8, n0 = (bx % tilesN) * 32;
+    {
+        const int m = m0 + rl, n = n0 + 4 * nq;
+        const bool ok = (m < M && n < N);
+        const float* q = P + (ok ? (long long)m * N + n : 0);
+        const int S4 = S & ~3;
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+        int k = j;
+        for (; k + 28 < S4; k += 32) {
+            const float4 v0 = RIH_RW_LD(q, k), v1 = RIH_RW_LD(q, k + 4), v2 = RIH_RW_LD(q, k + 8), v3 = RIH_RW_LD(q, k + 12);
+            const float4 v4 = RIH_RW_LD(q, k + 16), v5 = RIH_RW_LD(q, k + 20), v6 = RIH_RW_LD(q, k + 24), v7 = RIH_RW_LD(q, k + 28);
+            RIH_RW_ADD(a, v0) RIH_RW_ADD(a, v1) RIH_RW_ADD(a, v2) RIH_RW_ADD(a, v3)
+            RIH_RW_ADD(a, v4) RIH_RW_ADD(a, v5) RIH_RW_ADD(a, v6) RIH_RW_ADD(a, v7)
+        }
+        for (; k < S4; k += 4) { const float4 v = RIH_RW_LD(q, k); RIH_RW_ADD(a, v) }
+        if (j == 0)
+            for (k = S4; k < S; ++k) { const float4 v = RIH_RW_LD(q, k); RIH_RW_ADD(a, v) }
+        const float4 x = reduce_shfl_add(a, 8);         // j = 0: a0 + a1, j = 2: a2 + a3
+        const float4 y = reduce_shfl_add(x, 16);        // j = 0: (a0 + a1) + (a2 + a3)
+        if (j == 0) {
+            dtile[rl][4 * nq] = ok ? y.x : 0.f; dtile[rl][4 * nq + 1] = ok ? y.y : 0.f;
+            dtile[rl][4 * nq + 2] = ok ? y.z : 0.f; dtile[rl][4 * nq + 3] = ok ? y.w : 0.f;
+        }
+    }
+    __syncthreads();
+    {
+        const int m = m0 + (threadIdx.x & 7), n = n0 + (threadIdx.x >> 3);
+        if (m < M && n < N) {
+            const int tap = m / Cin, ci = m - tap * Cin;
+            if (ci < CinValid) {
+                const long long o = ((long long)n * pitch + ci) * taps + tap;
+                const float v = dtile[threadIdx.x & 7][threadIdx.x >> 3];
+                dst[o] = accumulate ? dst[o] + v : v;
+            }
+        }
+    }
+}
+#undef RIH_RW_ADD
+#undef RIH_RW_LD
+#undef RIH_RW_FIN
+// the kernel of one reduction: 0 = splitk_reduce_block (the decoder's N = 3 heads, unaligned slabs, anything unusual), 1 = wide,
+// 2 = deep
+__device__ __forceinline__ void splitk_reduce_any(int path, const float* __restrict__ P, int S, int Mp, int M, int N,
+                                                  float* __restrict__ dst, int Cin, int taps, int CinValid, int accumulate,
+                                                  float* __restrict__ db, int ntiles, int bx, int CinPitch) {
+    if (path == 1) splitk_reduce_wide_block(P, S, Mp, M, N, dst, Cin, taps, CinValid, accumulate, db, ntiles, bx, CinPitch);
+    else if (path == 2) splitk_reduce_deep_block(P, S, Mp, M, N, dst, Cin, taps, CinValid, accumulate, db, ntiles, bx, CinPitch);
+    else splitk_reduce_block(P, S, Mp, M, N, dst, Cin, taps, CinValid, accumulate, db, ntiles, bx, CinPitch);
+}
+inline int reduce_path(const float* P, int S, int M, int N, int Cin, int taps, int CinValid) {
+    if (N % 4 != 0 || ((uintptr_t)P % 16) != 0 || taps > RW_ROWS || CinValid > Cin || (long long)taps * Cin != M) return 0;
+    return S >= RW_DEEP ? 2 : 1;
+}
+inline long long reduce_tiles(int path, int M, int N, int taps, int CinValid) {
+    if (path != 1) return (long long)((M + 7) / 8) * ((N + 31) / 32);
+    const int cr = reduce_wide_ci(taps);
+    return (long long)((CinValid + cr - 1) / cr) * ((N + RW_NT - 1) / RW_NT);
+}
+
 __global__ __launch_bounds__(256) void splitk_reduce_fused_kernel(const float* __restrict__ P, int S, int Mp, int M, int N,
                                                                   float* __restrict__ dst, int Cin, int taps, int CinValid,
                                                                   int accumulate, float* __restrict__ db, int ntiles,
-                                                                  long long sP, long long sDst, long long sDb) {
+                                                                  long long sP, long long sDst, long long sDb, int path) {
     // blockIdx.y = independent reductions of one launch (paired left/right-hand weight gradients)
     P += blockIdx.y * sP;
     dst += blockIdx.y * sDst;
     if (db != nullptr) db += blockIdx.y * sDb;
-    splitk_reduce_block(P, S, Mp, M, N, dst, Cin, taps, CinValid, accumulate, db, ntiles, (int)blockIdx.x);
+    splitk_reduce_any(path, P, S, Mp, M, N, dst, Cin, taps, CinValid, accumulate, db, ntiles, (int)blockIdx.x, 0);
 }
 
 // Many independent reductions in ONE launch (rih_splitk_reduce_multi): the descriptors travel by value in the kernel
@@ -1274,8 +1465,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_multi_kernel(const ReducePa
     int i = 0;
     while (i + 1 < pk.n && b >= pk.first[i + 1]) ++i;
     const rih_reduce_desc& d = pk.d[i];
-    splitk_reduce_block(d.P, d.S, d.Mp, d.M, d.N, d.dst, d.Cin, d.taps, d.CinValid, d.accumulate, d.db, pk.ntiles[i],
-                        b - pk.first[i], d.CinPitch);
+    // d.reserved here: the path the launcher chose (reduce_path), not the caller's field
+    splitk_reduce_any(d.reserved, d.P, d.S, d.Mp, d.M, d.N, d.dst, d.Cin, d.taps, d.CinValid, d.accumulate, d.db, pk.ntiles[i],
+                      b - pk.first[i], d.CinPitch);
 }
 
 // Forward split-K finish: C[m*ldc+n] = act(alpha * sum_s P[s][m][n] + bias[n] + R[m*ldr+n])
@@ -1344,11 +1536,71 @@ struct PackPack {
     int n;
 };
 static_assert(sizeof(PackPack) <= 4096, "kernel argument limit");
+// The same element maps as a tiled transpose through LDS ("wide" path, taps <= PW_TAPS): a block stages the weights of a
+// (co range) x (ci range) x all taps tile -- for each co one contiguous span of the OIHW parameter, a wavefront per co -- and
+// writes runs along the operand's fastest dimension, co in mode 0 and ci in mode 1, a wavefront per run, instead of one useful
+// float per fetched sector.  No division per element: the loops follow the two layouts.
+constexpr int PW_TAPS = 63;
+constexpr int PW_LDS = 4096;            // floats
+struct PackTile { int cob, cib, lp; };  // co per tile, ci per tile, LDS pitch of one co (odd)
+__host__ __device__ inline PackTile pack_wide_tile(int taps, int mode) {
+    PackTile t;
+    if (mode == 0) {        // runs of 64 co
+        t.cob = 64;
+        t.cib = 63 / taps;
+    } else {                // runs of 64 ci
+        t.cib = 64;
+        t.cob = PW_LDS / (64 * taps + 1) > 64 ? 64 : PW_LDS / (64 * taps + 1);
+    }
+    t.lp = (t.cib * taps) | 1;
+    return t;
+}
+__device__ __forceinline__ void pack_wide_block(const rih_pack_desc& d, int bx) {
+    __shared__ float ptile[PW_LDS];
+    const int taps = d.KH * d.KW;
+    const PackTile pt = pack_wide_tile(taps, d.mode);
+    const int tilesCi = (d.CinPad + pt.cib - 1) / pt.cib;
+    const int co0 = (bx / tilesCi) * pt.cob, ci0 = (bx % tilesCi) * pt.cib;
+    const int cobv = d.Cout - co0 < pt.cob ? d.Cout - co0 : pt.cob;
+    const int cibv = d.CinPad - ci0 < pt.cib ? d.CinPad - ci0 : pt.cib;
+    const int span = cibv * taps;                                       // floats of one co in the tile, (ci, tap) order
+    const int live = d.Cin - ci0 < cibv ? (d.Cin - ci0 > 0 ? (d.Cin - ci0) * taps : 0) : span;    // the rest are zero rows
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll 4
+    for (int c = wave; c < cobv; c += 4) {
+        const long long src = ((long long)(co0 + c) * d.Cin + ci0) * taps;
+        for (int e = lane; e < span; e += 64) ptile[c * pt.lp + e] = e < live ? d.w[src + e] : 0.f;
+    }
+    __syncthreads();
+    if (d.mode == 0) {      // dst[(tap * CinPad + ci) * Cout + co]
+        if (lane < cobv)
+            for (int tap = 0; tap < taps; ++tap)
+                for (int cj = wave; cj < cibv; cj += 4)
+                    d.dst[((long long)tap * d.CinPad + ci0 + cj) * d.Cout + co0 + lane] = ptile[lane * pt.lp + cj * taps + tap];
+    } else if (lane < cibv) {               // dst[((th * Tw + tw) * Cout + co) * CinPad + ci]
+        for (int th = 0; th < d.Th; ++th)
+            for (int tw = 0; tw < d.Tw; ++tw) {
+                const int tap = (d.kh0 + d.step * (d.Th - 1 - th)) * d.KW + d.kw0 + d.step * (d.Tw - 1 - tw);
+                for (int c = wave; c < cobv; c += 4)
+                    d.dst[((long long)(th * d.Tw + tw) * d.Cout + co0 + c) * d.CinPad + ci0 + lane] =
+                        ptile[c * pt.lp + lane * taps + tap];
+            }
+    }
+}
+inline long long pack_wide_tiles(const rih_pack_desc& d) {
+    const PackTile pt = pack_wide_tile(d.KH * d.KW, d.mode);
+    return (long long)((d.Cout + pt.cob - 1) / pt.cob) * ((d.CinPad + pt.cib - 1) / pt.cib);
+}
+
 __global__ __launch_bounds__(256) void pack_conv_weight_multi_kernel(const PackPack pk) {
     const int b = (int)blockIdx.x;
     int k = 0;
     while (k + 1 < pk.n && b >= pk.first[k + 1]) ++k;
     const rih_pack_desc& d = pk.d[k];
+    if (d.reserved) {       // here: the path the launcher chose (1 = wide), not the caller's field
+        pack_wide_block(d, b - pk.first[k]);
+        return;
+    }
     const int nb = pk.first[k + 1] - pk.first[k];
     const int taps = d.KH * d.KW;
     const long long total = (d.mode == 0) ? (long long)taps * d.CinPad * d.Cout : (long long)d.Th * d.Tw * d.Cout * d.CinPad;
@@ -1393,7 +1645,12 @@ extern "C" int rih_pack_conv_weight_multi(const rih_pack_desc* descs, int n, voi
             const long long el = (d.mode == 0) ? (long long)d.KH * d.KW * d.CinPad * d.Cout : (long long)d.Th * d.Tw * d.Cout * d.CinPad;
             long long nb = (el + 4095) / 4096;        // 16 elements per thread: these are latency-, not bandwidth-sized
             if (nb > 1024) nb = 1024;
+            // rih_pack_desc.reserved != 0 keeps a descriptor on the reference path (tests, measurements)
+            const bool wide = d.reserved == 0 && (long long)d.KH * d.KW <= PW_TAPS;
+            if (wide) nb = pack_wide_tiles(d);
+            if (total + nb > 0x7fffffffLL) return RIH_EINVAL;
             pk.d[i] = d;
+            pk.d[i].reserved = wide ? 1 : 0;
             pk.first[i] = total;
             total += (int)nb;
         }
@@ -1707,12 +1964,14 @@ extern "C" int rih_splitk_reduce_bias_batched(const float* P, int S, int Mp, int
     if (!P || !dst || S < 1 || M < 1 || Mp < M || N < 1 || Cin < 1 || taps < 1 || CinValid < 1) return RIH_EINVAL;
     if (db && Mp < M + 1) return RIH_EINVAL;
     if (nb < 1 || nb > 65535) return RIH_EINVAL;
-    const long long tiles = (long long)((M + 7) / 8) * ((N + 31) / 32);
+    // every slice of the batch must meet the wide path's alignment
+    const int path = (nb == 1 || sP % 4 == 0) ? reduce_path(P, S, M, N, Cin, taps, CinValid) : 0;
+    const long long tiles = reduce_tiles(path, M, N, taps, CinValid);
     const long long blocks = tiles + (db ? (N + 255) / 256 : 0);
     if (blocks > 0x7fffffffLL) return RIH_EINVAL;
     hipLaunchKernelGGL(splitk_reduce_fused_kernel, dim3((unsigned)blocks, (unsigned)nb), dim3(256), 0, (hipStream_t)stream,
                        P, S, Mp, M, N, dst, Cin, taps, CinValid, accumulate, db, (int)tiles, (long long)sP,
-                       (long long)sDst, (long long)sDb);
+                       (long long)sDst, (long long)sDb, path);
     return (int)hipGetLastError();
 }
 
@@ -1731,8 +1990,11 @@ extern "C" int rih_splitk_reduce_multi(const rih_reduce_desc* descs, int n, void
         long long total = 0;
         for (int i = 0; i < pk.n; ++i) {
             const rih_reduce_desc& d = descs[base + i];
-            const long long tiles = (long long)((d.M + 7) / 8) * ((d.N + 31) / 32);
+            // rih_reduce_desc.reserved != 0 keeps a descriptor on the reference path (tests, measurements)
+            const int path = d.reserved == 0 ? reduce_path(d.P, d.S, d.M, d.N, d.Cin, d.taps, d.CinValid) : 0;
+            const long long tiles = reduce_tiles(path, d.M, d.N, d.taps, d.CinValid);
             pk.d[i] = d;
+            pk.d[i].reserved = path;
             pk.ntiles[i] = (int)tiles;
             pk.first[i] = (int)total;
             total += tiles + (d.db ? (d.N + 255) / 256 : 0);
