@@ -735,7 +735,7 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc, opt state, adam dev entry (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 28
+#define RIH_ABI_VERSION 29
 #define RIH_ABI_NSIZES 14
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);
@@ -809,6 +809,15 @@ typedef struct rih_hconv_desc {
     int32_t relu, out_f32;
 } rih_hconv_desc;
 int rih_hconv(const rih_hconv_desc* d, void* stream);
+/* What rih_hconv would do with `d`, without launching anything: RIH_EINVAL where it refuses the descriptor, else
+ * RIH_HCONV_PLAN_BASE plus the flags of the kernel it launches (the same helper decides for both, including the
+ * RIH_HCONV_HALO / RIH_HCONV_GLDS / RIH_HCONV_BN switches of the process). */
+#define RIH_HCONV_PLAN_BASE 0x10  /* always set: a plan is positive */
+#define RIH_HCONV_PLAN_HALO 0x01  /* halo-resident 3x3 kernel (else the implicit GEMM) */
+#define RIH_HCONV_PLAN_TW16 0x02  /* halo: 16 x 16 pixel patches (else 8 x 32) */
+#define RIH_HCONV_PLAN_BN128 0x04 /* 128 output channels per workgroup (else 64) */
+#define RIH_HCONV_PLAN_REGS 0x08  /* implicit GEMM: operands staged through registers (else LDS-DMA) */
+int rih_hconv_plan(const rih_hconv_desc* d);
 /* fp32 OIHW -> fp16 [Cout][Kpad], k = (kh*KW + kw)*CinPad + ci, times scale[co] when scale != NULL; zero padded. */
 int rih_hpack_conv_weight(const float* w, const float* scale, void* dst, int Cout, int Cin, int KH, int KW, int CinPad,
                           int Kpad, void* stream);

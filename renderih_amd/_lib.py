@@ -122,6 +122,7 @@ SIGNATURES = {
                                  C.c_void_p]),
     'rih_prepare_labels': (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f, C.c_void_p, c_fl, c_i, c_fl, c_f, c_f, c_f, C.c_void_p]),
     'rih_hconv': (c_i, [C.POINTER(HConvDesc), C.c_void_p]),
+    'rih_hconv_plan': (c_i, [C.POINTER(HConvDesc)]),
     'rih_hpack_conv_weight': (c_i, [c_f, c_f, C.c_void_p, c_i, c_i, c_i, c_i, c_i, c_i, C.c_void_p]),
     'rih_hbn_fold': (c_i, [c_f, c_f, c_f, c_f, c_f, c_fl, c_f, c_f, c_i, C.c_void_p]),
     'rih_himage_nchw_to_nhwc8': (c_i, [c_f, C.c_void_p, c_i, c_i, c_i, c_i, C.c_void_p]),
@@ -262,7 +263,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 28     # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 29     # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 

@@ -19,8 +19,12 @@
 //   * epilogue: accumulators -> LDS (fp32) -> each lane owns 8 consecutive output channels of a pixel: + bias + residual
 //     (16-byte load) -> ReLU -> post scale/shift -> one 16-byte fp16 store (or two fp32 stores for the tensors handed to
 //     the fp32 mesh decoder).
-// STATUS: written after the round's GPU budget was spent; verified on the HIP-on-CPU harness (tests/test_half.py) against
-// torch on fp16-rounded operands; not yet run or measured on a GPU.  Opt-in (HandNET_GCN.use_fp16_backbone()).
+// STATUS: runs on gfx950 (BASELINE configs[4]); every instantiation is checked there against fp64 of its own fp16 operands, at
+// unit scale and away from it (tests/test_gpu_half_range.py; the same cases on the HIP-on-CPU harness, tests/test_half.py).
+// Measured: the MFMA takes fp16 subnormal operands exactly, the _Float16 conversions round to nearest even (subnormal results
+// included), clamp_h saturates at +-65504 where a plain cast gives inf; hbn_fold_kernel's sqrtf is not correctly rounded (last
+// place, a fifth of the channels), so the packed weights are not bit-reproducible from a CPU fold (DESIGN.md, fp16 numerics).
+// Opt-in (HandNET_GCN.use_fp16_backbone()).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -628,7 +632,15 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 
 }  // namespace
 
-extern "C" int rih_hconv(const rih_hconv_desc* d, void* stream) {
+// The one place that decides what rih_hconv does with a descriptor: RIH_EINVAL where it refuses, else RIH_HCONV_PLAN_BASE plus
+// the flags of the kernel it launches.  rih_hconv_plan hands the code out; rih_hconv dispatches on it.
+// RIH_HCONV_HALO=0: no halo-resident kernel (stride-1 3x3 convolutions on whole patches take the implicit GEMM too).
+// RIH_HCONV_GLDS=0: the implicit GEMM stages its operands through registers.
+// 128x64 tiles (three workgroups per CU instead of two; A is re-read per 64 columns) also for wide outputs when the reduction
+// is ONE k-tile: measured per shape at B = 256 (profiles/r04/c13_hconv_sweep_*.log) 1x1 64 -> 256 at 64x64 297 -> 272 us with
+// the residual, 279 -> 254 without; everywhere (RIH_HCONV_BN=64) the 3x3 convolutions lose 14-45 % and a forward 8 %.
+// RIH_HCONV_BN=128 switches the rule off.
+static int hconv_plan(const rih_hconv_desc* d) {
     if (!d || !d->x || !d->w || !d->y || !d->zero) return RIH_EINVAL;
     if (d->N < 1 || d->H < 1 || d->W < 1 || d->Cin < 8 || d->Cin % 8 != 0 || d->Cout < 1 || d->KH < 1 || d->KW < 1) return RIH_EINVAL;
     if (d->stride < 1 || d->pad < 0 || d->Ho < 1 || d->Wo < 1) return RIH_EINVAL;
@@ -640,6 +652,28 @@ extern "C" int rih_hconv(const rih_hconv_desc* d, void* stream) {
     if ((d->post_scale == nullptr) != (d->post_shift == nullptr)) return RIH_EINVAL;
     const long long M = (long long)d->N * d->Ho * d->Wo;
     if (M > 0x7fffffffLL || (long long)d->N * d->H * d->W > 0x7fffffffLL) return RIH_EINVAL;
+    static const bool halo = [] { const char* e = getenv("RIH_HCONV_HALO"); return !(e && e[0] == '0'); }();
+    const int tw = halo ? hconv3_tw(d) : 0;
+    if (tw != 0) {
+        const long long patches = (long long)d->N * (d->H / (256 / tw)) * (d->W / tw);
+        const int bn = (d->Cout % 128 == 0 && patches * (d->Cout / 128) >= 256) ? 128 : 64;
+        if (patches * (d->Cout / bn) > 0x7fffffffLL) return RIH_EINVAL;
+        return RIH_HCONV_PLAN_BASE | RIH_HCONV_PLAN_HALO | (tw == 16 ? RIH_HCONV_PLAN_TW16 : 0) | (bn == 128 ? RIH_HCONV_PLAN_BN128 : 0);
+    }
+    static const bool glds = [] { const char* e = getenv("RIH_HCONV_GLDS"); return !(e && e[0] == '0'); }();
+    static const int force_bn = [] { const char* e = getenv("RIH_HCONV_BN"); return e ? atoi(e) : 0; }();
+    const bool narrow = force_bn == 64 || (force_bn != 128 && d->Kpad <= BKH);
+    const int bn = (d->Cout > 64 && !narrow) ? 128 : 64;
+    if ((M + BM - 1) / BM * ((d->Cout + bn - 1) / bn) > 0x7fffffffLL) return RIH_EINVAL;
+    return RIH_HCONV_PLAN_BASE | (bn == 128 ? RIH_HCONV_PLAN_BN128 : 0) | (glds ? 0 : RIH_HCONV_PLAN_REGS);
+}
+
+extern "C" int rih_hconv_plan(const rih_hconv_desc* d) { return hconv_plan(d); }
+
+extern "C" int rih_hconv(const rih_hconv_desc* d, void* stream) {
+    const int plan = hconv_plan(d);
+    if (plan < 0) return plan;
+    const long long M = (long long)d->N * d->Ho * d->Wo;
     HConvArgs a;
     a.x = (const half_t*)d->x; a.w = (const half_t*)d->w; a.zero = (const half_t*)d->zero;
     a.bias = d->bias; a.post_scale = d->post_scale; a.post_shift = d->post_shift;
@@ -651,36 +685,22 @@ extern "C" int rih_hconv(const rih_hconv_desc* d, void* stream) {
     a.vec = al16(d->y) && d->ldy % (d->out_f32 ? 4 : 8) == 0 && (d->res == nullptr || (al16(d->res) && d->ldr % 8 == 0));
     a.cvec = (d->bias == nullptr || al16(d->bias)) && (d->post_scale == nullptr || (al16(d->post_scale) && al16(d->post_shift)));
     hipStream_t s = (hipStream_t)stream;
-    // stride-1 3x3 convolutions on whole patches: the halo-resident kernel (RIH_HCONV_HALO=0: the implicit GEMM below)
-    static const bool halo = [] { const char* e = getenv("RIH_HCONV_HALO"); return !(e && e[0] == '0'); }();
-    const int tw = halo ? hconv3_tw(d) : 0;
-    if (tw != 0) {
-        const long long patches = (long long)d->N * (d->H / (256 / tw)) * (d->W / tw);
-        const int bn = (d->Cout % 128 == 0 && patches * (d->Cout / 128) >= 256) ? 128 : 64;
-        const long long grid = patches * (d->Cout / bn);
-        if (grid > 0x7fffffffLL) return RIH_EINVAL;
+    const int bn = (plan & RIH_HCONV_PLAN_BN128) ? 128 : 64;
+    if (plan & RIH_HCONV_PLAN_HALO) {
+        const int tw = (plan & RIH_HCONV_PLAN_TW16) ? 16 : 32;
+        const long long grid = (long long)d->N * (d->H / (256 / tw)) * (d->W / tw) * (d->Cout / bn);
         if (tw == 32 && bn == 128) hipLaunchKernelGGL((hconv3_halo_kernel<32, 128>), dim3((unsigned)grid), dim3(H3_NT), 0, s, a);
         else if (tw == 32) hipLaunchKernelGGL((hconv3_halo_kernel<32, 64>), dim3((unsigned)grid), dim3(H3_NT), 0, s, a);
         else if (bn == 128) hipLaunchKernelGGL((hconv3_halo_kernel<16, 128>), dim3((unsigned)grid), dim3(H3_NT), 0, s, a);
         else hipLaunchKernelGGL((hconv3_halo_kernel<16, 64>), dim3((unsigned)grid), dim3(H3_NT), 0, s, a);
         return (int)hipGetLastError();
     }
-    const long long tilesM = (M + BM - 1) / BM;
-    static const bool glds = [] { const char* e = getenv("RIH_HCONV_GLDS"); return !(e && e[0] == '0'); }();
-    // 128x64 tiles (three workgroups per CU instead of two; A is re-read per 64 columns) also for wide outputs when the reduction
-    // is ONE k-tile: measured per shape at B = 256 (profiles/r04/c13_hconv_sweep_*.log) 1x1 64 -> 256 at 64x64 297 -> 272 us with
-    // the residual, 279 -> 254 without; everywhere (RIH_HCONV_BN=64) the 3x3 convolutions lose 14-45 % and a forward 8 %.
-    // RIH_HCONV_BN=128 switches the rule off.
-    static const int force_bn = [] { const char* e = getenv("RIH_HCONV_BN"); return e ? atoi(e) : 0; }();
-    const bool narrow = force_bn == 64 || (force_bn != 128 && d->Kpad <= BKH);
-    if (d->Cout > 64 && !narrow) {
-        const long long tiles = tilesM * ((d->Cout + 127) / 128);
-        if (tiles > 0x7fffffffLL) return RIH_EINVAL;
+    const bool glds = !(plan & RIH_HCONV_PLAN_REGS);
+    const long long tiles = (M + BM - 1) / BM * ((d->Cout + bn - 1) / bn);
+    if (bn == 128) {
         if (glds) hipLaunchKernelGGL((hconv_kernel<128, true>), dim3((unsigned)tiles), dim3(TPB), 0, s, a);
         else hipLaunchKernelGGL((hconv_kernel<128, false>), dim3((unsigned)tiles), dim3(TPB), 0, s, a);
     } else {
-        const long long tiles = tilesM * ((d->Cout + 63) / 64);
-        if (tiles > 0x7fffffffLL) return RIH_EINVAL;
         if (glds) hipLaunchKernelGGL((hconv_kernel<64, true>), dim3((unsigned)tiles), dim3(TPB), 0, s, a);
         else hipLaunchKernelGGL((hconv_kernel<64, false>), dim3((unsigned)tiles), dim3(TPB), 0, s, a);
     }

@@ -18,7 +18,8 @@ Numerics: fp16 storage (11-bit significand) of weights and activations, fp32 acc
 1e-4 parity path -- that is the fp32 path, which stays the default; `HandNET_GCN.use_fp16_backbone()` opts in for inference.
 The snapshot is taken when it is built: call it again after loading or changing weights.
 
-STATUS: harness-verified (tests/test_half.py), not yet run on a GPU (written after the round's GPU budget was spent).
+STATUS: runs on the GPU (bench.py --config5); kernels checked there and on the host harness at unit scale and away from it
+(tests/test_gpu_half_range.py, tests/test_half.py; what was measured: DESIGN.md, fp16 numerics).
 """
 import ctypes as C
 
@@ -36,6 +37,8 @@ def _cdiv(a, b):
 
 
 _ZERO = {}
+# = RIH_HCONV_PLAN_* of include/renderih_amd.h: what rih_hconv_plan returns
+PLAN_BASE, PLAN_HALO, PLAN_TW16, PLAN_BN128, PLAN_REGS = 0x10, 0x01, 0x02, 0x04, 0x08
 TALLY = None        # set to {'flop': 0.0, 'bytes': 0.0, 'launches': 0} to count the convolutions' algorithmic work
 
 
@@ -100,7 +103,8 @@ class PackedConv:
                                          self.Cout, self.Cin_w, self.KH, self.KW, self.Cin, self.Kpad, ops._stream()),
               'rih_hpack_conv_weight')
 
-    def __call__(self, x, relu=False, res=None, out=None, out_f32=False):
+    def _desc(self, x, relu, res, out, out_f32):
+        """The rih_hconv descriptor of one call (and the output tensor it points at)."""
         ops._chk(x, res, dtype=F16)
         ops._chk(out, dtype=None)
         N, H, W, Cx, ldx = _geom(x)
@@ -124,6 +128,16 @@ class PackedConv:
         d.N, d.H, d.W, d.Cin, d.Cout, d.KH, d.KW = N, H, W, self.Cin, self.Cout, self.KH, self.KW
         d.stride, d.pad, d.Ho, d.Wo, d.ldx, d.ldy, d.Kpad = self.stride, self.pad, Ho, Wo, ldx, ldy, self.Kpad
         d.relu, d.out_f32 = int(relu), int(out_f32)
+        return d, out
+
+    def plan(self, x, relu=False, res=None, out=None, out_f32=False):
+        """The kernel rih_hconv launches for this call (PLAN_* flags), without launching it; negative where it refuses."""
+        return ops._L().rih_hconv_plan(C.byref(self._desc(x, relu, res, out, out_f32)[0]))
+
+    def __call__(self, x, relu=False, res=None, out=None, out_f32=False):
+        d, out = self._desc(x, relu, res, out, out_f32)
+        N, H, W = x.shape[:3]
+        Ho, Wo = out.shape[1:3]
         # algorithmic work of this launch (true Cin of the weights, no padding)
         flop = 2.0 * N * Ho * Wo * self.Cout * self.KH * self.KW * self.Cin_w
         nbytes = 2.0 * (N * H * W * self.Cin_w + self.Cout * self.KH * self.KW * self.Cin_w) + \

@@ -8,6 +8,7 @@ caller's tensors through their raw pointers.  It is NOT a product fallback -- on
 """
 import contextlib
 import ctypes as C
+import os
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -852,10 +853,51 @@ class EmulatedLib:
             self._hview(d.y, pixels, d.ldy, d.Cout)[:] = np.clip(y, -65504, 65504).astype(np.float16)
         return 0
 
+    def rih_hconv_plan(self, dref):
+        """The kernel choice of rih_hconv restated (RIH_HCONV_PLAN_* of the header): base 0x10, halo 1, 16 x 16 patches 2, 128
+        output channels per workgroup 4, register staging 8; -1 where the entry point refuses."""
+        d = dref._obj
+        al16 = lambda p: p is not None and p % 16 == 0
+        if not (d.x and d.w and d.y and d.zero):
+            return -1
+        if d.N < 1 or d.H < 1 or d.W < 1 or d.Cin < 8 or d.Cin % 8 or d.Cout < 1 or d.KH < 1 or d.KW < 1:
+            return -1
+        if d.stride < 1 or d.pad < 0 or d.Ho < 1 or d.Wo < 1:
+            return -1
+        if d.Ho != (d.H + 2 * d.pad - d.KH) // d.stride + 1 or d.Wo != (d.W + 2 * d.pad - d.KW) // d.stride + 1:
+            return -1
+        if d.Kpad % 64 or d.Kpad < d.KH * d.KW * d.Cin:
+            return -1
+        if d.ldx < d.Cin or d.ldx % 8 or d.ldy < d.Cout or not (al16(d.x) and al16(d.w) and al16(d.zero)):
+            return -1
+        if (d.res and d.ldr < d.Cout) or bool(d.post_scale) != bool(d.post_shift):
+            return -1
+        M = d.N * d.Ho * d.Wo
+        if M > 0x7fffffff or d.N * d.H * d.W > 0x7fffffff:
+            return -1
+        env = lambda k: os.environ.get(k, '')
+        tw = 0
+        if (not env('RIH_HCONV_HALO').startswith('0') and (d.KH, d.KW, d.stride, d.pad) == (3, 3, 1, 1) and not d.res
+                and d.Cin % 64 == 0 and d.Cout % 64 == 0 and d.ldy % (4 if d.out_f32 else 8) == 0 and al16(d.y)):
+            tw = 32 if (d.H % 8 == 0 and d.W % 32 == 0) else 16 if (d.H % 16 == 0 and d.W % 16 == 0) else 0
+        if tw:
+            patches = d.N * (d.H // (256 // tw)) * (d.W // tw)
+            bn = 128 if (d.Cout % 128 == 0 and patches * (d.Cout // 128) >= 256) else 64
+            if patches * (d.Cout // bn) > 0x7fffffff:
+                return -1
+            return 0x10 | 1 | (2 if tw == 16 else 0) | (4 if bn == 128 else 0)
+        force = env('RIH_HCONV_BN')
+        narrow = force == '64' or (force != '128' and d.Kpad <= 64)
+        bn = 128 if (d.Cout > 64 and not narrow) else 64
+        if -(-M // 128) * (-(-d.Cout // bn)) > 0x7fffffff:
+            return -1
+        return 0x10 | (4 if bn == 128 else 0) | (8 if env('RIH_HCONV_GLDS').startswith('0') else 0)
+
     def rih_hpack_conv_weight(self, w, scale, dst, Cout, Cin, KH, KW, CinPad, Kpad, stream):
         W = _f(w, Cout * Cin * KH * KW).reshape(Cout, Cin, KH, KW).copy()
         if scale:
-            W = W * _f(scale, Cout)[:, None, None, None]
+            with np.errstate(over='ignore'):          # beyond fp32: inf, clipped below as the kernel clips it
+                W = W * _f(scale, Cout)[:, None, None, None]
         out = np.zeros((Cout, Kpad), np.float16)
         packed = np.zeros((Cout, KH, KW, CinPad), np.float32)
         packed[..., :Cin] = W.transpose(0, 2, 3, 1)
@@ -874,7 +916,7 @@ class EmulatedLib:
     def rih_himage_nchw_to_nhwc8(self, img, out, N, Cn, H, W, stream):
         x = _f(img, N * Cn * H * W).reshape(N, Cn, H, W)
         o = np.zeros((N, H, W, 8), np.float16)
-        o[..., :Cn] = x.transpose(0, 2, 3, 1).astype(np.float16)
+        o[..., :Cn] = np.clip(x.transpose(0, 2, 3, 1), -65504, 65504).astype(np.float16)     # saturates, as the kernel does
         self._h(out, o.size)[:] = o.ravel()
         return 0
 

@@ -2,8 +2,10 @@
   * the kernels themselves, compiled for the host (tests/hipcpu: fibers, emulated v_mfma_f32_32x32x16_f16 and LDS-DMA with
     the lane-linear destination rule and deferred landing), against torch on identically fp16-rounded operands;
   * the host logic of HalfBackbone (BN folding, in-place channel concatenation, stage order) through the numpy/torch
-    restatement of the entry points (tests/abi_emulator.py), against the fp32 model.
-The same checks run on the GPU from tests/test_gpu_paths.py."""
+    restatement of the entry points (tests/abi_emulator.py), against the fp32 model;
+  * both away from unit scale (tests/half_cases.py: subnormal weights and activations, dead channels, saturation), the other
+    entry points at their edges and the whole backbone on checkpoint-like BatchNorm statistics, against fp64.
+The same checks run on the GPU from tests/test_gpu_paths.py and tests/test_gpu_half_range.py."""
 import os
 import sys
 
@@ -24,40 +26,120 @@ def _q(t):
     return t.to(F16).float()
 
 
-def conv_case(dev, N, H, W, Cin, Cout, k, stride, pad, order, relu, res, out_f32, x_pad=0, y_pad=0, seed=0, cin_w=None):
-    """One PackedConv call against F.conv2d on fp16-rounded operands (fp32 accumulate), fp32 epilogue, final rounding."""
+def scaled(t, s):
+    """t * s, and t itself at s == 1 (the idiom of tests/test_gpu_ops.py): the default data stays bit for bit what it was."""
+    return t if s == 1.0 else t * s
+
+
+def _uniform(u, rng):
+    """u in [0, 1) mapped onto rng; the default range keeps the historical expression."""
+    return u + 0.5 if tuple(rng) == (0.5, 1.5) else u * (rng[1] - rng[0]) + rng[0]
+
+
+SUBNORMAL = 2.0 ** -14          # below it an fp16 value is subnormal
+HALF_MAX = 65504.0
+HALF_OVER = 65520.0             # from here on round-to-nearest leaves the fp16 range: the kernels saturate, torch's cast gives inf
+
+
+def half_step(m):
+    """One fp16 step at magnitude m > 0 (fp64 tensor): 2^(floor(log2 m) - 10), 2^-24 in the subnormal range."""
+    e = torch.frexp(m)[1] - 1
+    return torch.ldexp(torch.ones_like(m), e.clamp_min(-14) - 10)
+
+
+def q_half(ref64):
+    """The correctly rounded, saturated fp16 value of an fp64 tensor (as fp64)."""
+    return ref64.clamp(-HALF_MAX, HALF_MAX).to(F16).double()
+
+
+def check_range(got, ref64, out_f32, what=''):
+    """The bar of the off-unit-scale cases, relative to max|ref64| with no floor.  fp32 output: error <= 1e-5 max|ref64| (the
+    unit-scale tolerance).  fp16 output: finite; exactly +-65504 where |ref64| >= 65520; elsewhere within one fp16 step at
+    max(|ref64|, 2^-10 max|ref64|) of the correctly rounded value, and >= 97 % of those outputs ARE that value."""
+    got = got.double()
+    top = ref64.abs().max().item()
+    assert top > 0 and bool(torch.isfinite(got).all()), (what, top)
+    m = {'max_ref': top}
+    if out_f32:
+        m['err'] = ((got - ref64).abs().max().item()) / top
+        print('half_range %s fp32 | max err / max|ref64| = %.3g (bar 1e-5)' % (what, m['err']))
+        assert m['err'] <= 1e-5, (what, m)
+        return m
+    sat = ref64.abs() >= HALF_OVER
+    q = q_half(ref64)
+    steps = ((got - q).abs() / half_step(ref64.abs().clamp_min(2.0 ** -10 * top)))[~sat]
+    m.update(saturated=sat.double().mean().item(), steps=steps.max().item() if steps.numel() else 0.0,
+             exact=(got == q)[~sat].double().mean().item() if steps.numel() else 1.0,
+             sat_ok=bool((got[sat] == torch.sign(ref64[sat]) * HALF_MAX).all()))
+    print('half_range %s fp16 | saturated %.4f (exact +-65504: %s) | worst %.3g fp16 steps (bar 1) | share correctly rounded %.5f '
+          '(bar 0.97)' % (what, m['saturated'], m['sat_ok'], m['steps'], m['exact']))
+    assert m['sat_ok'] and m['steps'] <= 1.0 and m['exact'] >= 0.97, (what, m)
+    return m
+
+
+def conv_case(dev, N, H, W, Cin, Cout, k, stride, pad, order, relu, res, out_f32, x_pad=0, y_pad=0, seed=0, cin_w=None,
+              xs=1.0, ws=1.0, rs=1.0, gamma=(0.5, 1.5), var=(0.5, 1.5), zero_gamma=(), bar='unit', guard=None,
+              expect_plan=None, run=True, what=''):
+    """One PackedConv call against F.conv2d on fp16-rounded operands (fp32 accumulate), fp32 epilogue, final rounding.
+    xs / ws / rs scale activations, weights and the residual; gamma / var are the ranges of the BatchNorm weight and running
+    variance, zero_gamma channels whose weight is exactly 0.  bar='range': against an fp64 convolution of the same fp16
+    operands with check_range; `guard` names the precondition the data must meet on the reference side ('sub_w_partial',
+    'sub_w_all', 'sub_x', 'saturate').  expect_plan: what rih_hconv_plan must answer for the call's descriptor.  out_f32 may
+    be 'both' (one reference, two launches).  run=False: only the plan is asked for.  Returns what was measured."""
     g = torch.Generator().manual_seed(seed)
     cin_w = cin_w or Cin
     conv = nn.Conv2d(cin_w, Cout, k, stride, pad, bias=(order is None)).to(dev)
     bn = None
     with torch.no_grad():
-        conv.weight.copy_(torch.randn(conv.weight.shape, generator=g) * (2.0 / (cin_w * k * k)) ** 0.5)
+        conv.weight.copy_(scaled(torch.randn(conv.weight.shape, generator=g) * (2.0 / (cin_w * k * k)) ** 0.5, ws))
         if conv.bias is not None:
             conv.bias.copy_(torch.randn(Cout, generator=g) * 0.1)
         if order is not None:
             bn = nn.BatchNorm2d(Cout).to(dev).eval()
-            bn.weight.copy_(torch.rand(Cout, generator=g) + 0.5)
+            bn.weight.copy_(_uniform(torch.rand(Cout, generator=g), gamma))
             bn.bias.copy_(torch.randn(Cout, generator=g) * 0.2)
             bn.running_mean.copy_(torch.randn(Cout, generator=g) * 0.2)
-            bn.running_var.copy_(torch.rand(Cout, generator=g) + 0.5)
+            bn.running_var.copy_(_uniform(torch.rand(Cout, generator=g), var))
+            for c in zero_gamma:
+                bn.weight[c] = 0.0
     pc = half.PackedConv(conv, bn, order, cin_pad=Cin)
     xw = torch.zeros(N, H, W, Cin + x_pad, dtype=F16, device=dev)
-    xw[..., :cin_w] = torch.randn(N, H, W, cin_w, generator=g).to(F16).to(dev)
+    xw[..., :cin_w] = scaled(torch.randn(N, H, W, cin_w, generator=g), xs).to(F16).to(dev)
     if x_pad:
         xw[..., Cin:] = 7.0                           # neighbours of the slice must not leak in
     x = xw[..., :Cin]
     Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-    r = torch.randn(N, Ho, Wo, Cout, generator=g).to(F16).to(dev) if res else None
-    ydt = torch.float32 if out_f32 else F16
-    yw = torch.full((N, Ho, Wo, Cout + y_pad), -3.0, dtype=ydt, device=dev)
-    y = pc(x, relu=relu, res=r, out=yw[..., :Cout], out_f32=out_f32)
-    if y_pad:
-        assert bool((yw[..., Cout:] == -3.0).all()), 'wrote outside the channel slice'
-    # reference (always on the CPU: plain fp32 arithmetic whatever the device under test)
+    r = scaled(torch.randn(N, Ho, Wo, Cout, generator=g), rs).to(F16).to(dev) if res else None
+    outs = {}
+    for f32 in ((False, True) if out_f32 == 'both' else (bool(out_f32),)):
+        yw = torch.full((N, Ho, Wo, Cout + y_pad), -3.0, dtype=torch.float32 if f32 else F16, device=dev)
+        if expect_plan is not None:
+            plan = pc.plan(x, relu=relu, res=r, out=yw[..., :Cout], out_f32=f32)
+            assert plan == expect_plan, 'rih_hconv_plan %#x, expected %#x (%s)' % (plan, expect_plan, what)
+        if not run:
+            continue
+        y = pc(x, relu=relu, res=r, out=yw[..., :Cout], out_f32=f32)
+        if y_pad:
+            assert bool((yw[..., Cout:] == -3.0).all()), 'wrote outside the channel slice'
+        outs[f32] = y.to('cpu')
+    if not run:
+        return {}
+    # reference (always on the CPU: plain arithmetic whatever the device under test)
     cpu = torch.device('cpu')
-    conv, x, y = conv.to(cpu), x.to(cpu), y.to(cpu)
+    conv, x = conv.to(cpu), x.to(cpu)
     bn = None if bn is None else bn.to(cpu)
     r = None if r is None else r.to(cpu)
+    if bar == 'range':
+        ref, wq = _range_reference(conv, bn, order, x[..., :cin_w], r, relu, stride, pad, pc)
+        _range_guard(guard, wq, x[..., :cin_w], ref, what)
+        measured = {}
+        for f32, y in outs.items():
+            measured[f32] = check_range(y, ref, f32, what)
+            for c in zero_gamma:                      # scale 0: the output is the shift (+ residual), to the bit
+                want = ref[..., c].float() if f32 else q_half(ref[..., c]).to(F16)
+                assert torch.equal(y[..., c], want), (what, 'channel with gamma = 0', c)
+        return measured
+    assert guard is None and not zero_gamma
     with torch.no_grad():
         if order == 'conv-bn':
             s = bn.weight / torch.sqrt(bn.running_var + bn.eps)
@@ -77,14 +159,75 @@ def conv_case(dev, N, H, W, Cin, Cout, k, stride, pad, order, relu, res, out_f32
         if order == 'conv-relu-bn':
             s = bn.weight / torch.sqrt(bn.running_var + bn.eps)
             ref = ref * s + (bn.bias - bn.running_mean * s)
-    got = y.float()
-    tol = 1e-5 if out_f32 else 1.5e-3                 # fp16 output: one rounding (2^-11 relative) + summation order
-    err = (got - ref).abs().max().item()
-    scale = ref.abs().max().item()
-    assert err <= tol * max(scale, 1.0) + 1e-6, (err, scale)
-    if not out_f32:                                   # almost all outputs are THE correctly rounded value
-        exact = (got == _q(ref)).float().mean().item()
-        assert exact > 0.97, exact
+    measured = {}
+    for f32, y in outs.items():
+        got = y.float()
+        tol = 1e-5 if f32 else 1.5e-3                 # fp16 output: one rounding (2^-11 relative) + summation order
+        err = (got - ref).abs().max().item()
+        scale = ref.abs().max().item()
+        assert err <= tol * max(scale, 1.0) + 1e-6, (err, scale)
+        measured[f32] = {'err': err, 'max_ref': scale}
+        if not f32:                                   # almost all outputs are THE correctly rounded value
+            exact = (got == _q(ref)).float().mean().item()
+            assert exact > 0.97, exact
+            measured[f32]['exact'] = exact
+    return measured
+
+
+def _range_reference(conv, bn, order, x, r, relu, stride, pad, pc):
+    """bar='range' of conv_case: fp64 convolution of the SAME fp16 operands, every later operation in fp64 too.  The operands are
+    the ones the kernel reads -- the packed weights and the fp32 epilogue constants of `pc`, read back -- after they have been
+    checked against the fold in fp64: a packed weight is the fp16 rounding (to nearest, clipped to +-65504 as hpack_weight_kernel
+    documents) of w * gamma / sqrt(var + eps) up to the fp32 arithmetic in between, 4 x 2^-24 relative.  (The fold is NOT bit
+    for bit the fp32 torch expression on the hardware: sqrtf differs in the last place in a fifth of the channels, measured
+    1.0e-7 from fp64 where torch's fp32 on the CPU is 1.1e-7; a weight in 30 000 then rounds to the neighbouring fp16 value.)
+    Returns the reference and the reference side's own rounding of the folded weights (for the regime guards)."""
+    FP32 = 4 * 2.0 ** -24
+    Cout, cin_w, k = conv.out_channels, conv.in_channels, conv.kernel_size[0]
+    with torch.no_grad():
+        s64 = t64 = slack = None
+        if bn is not None:
+            s64 = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+            t64 = bn.bias.double() - bn.running_mean.double() * s64
+            slack = FP32 * (bn.bias.double().abs() + (bn.running_mean.double() * s64).abs()) + 1e-45
+        w64 = (conv.weight.double() * s64[:, None, None, None] if order == 'conv-bn' else conv.weight.double()).clamp(-HALF_MAX, HALF_MAX)
+        packed = pc.w.cpu()
+        wk = packed[:, :k * k * pc.Cin].reshape(Cout, k, k, pc.Cin)
+        assert bool((wk[..., cin_w:] == 0).all()) and bool((packed[:, k * k * pc.Cin:] == 0).all()), 'padding of the packed weights'
+        wk = wk[..., :cin_w].permute(0, 3, 1, 2).double()
+        assert bool(((wk - w64).abs() <= 0.5 * half_step(w64.abs().clamp_min(2.0 ** -24)) + FP32 * w64.abs()).all()), 'packed weights'
+        bias = None if pc.bias is None else pc.bias.cpu().double()
+        if order == 'conv-bn':
+            assert bool(((bias - t64).abs() <= slack).all()), 'folded bias'
+        elif conv.bias is not None:
+            assert torch.equal(bias, conv.bias.double())
+        ref = F.conv2d(x.double().permute(0, 3, 1, 2), wk, None, stride, pad).permute(0, 2, 3, 1)
+        if bias is not None:
+            ref = ref + bias
+        if r is not None:
+            ref = ref + r.double()
+        if relu:
+            ref = ref.clamp_min(0)
+        if order == 'conv-relu-bn':
+            ps, pt = pc.post_scale.cpu().double(), pc.post_shift.cpu().double()
+            assert bool(((ps - s64).abs() <= FP32 * s64.abs()).all()) and bool(((pt - t64).abs() <= slack).all()), 'post scale / shift'
+            ref = ref * ps + pt
+    return ref.contiguous(), w64.to(F16)
+
+
+def _range_guard(guard, wq, x, ref, what):
+    """The precondition of a regime, on the reference side: the case is not vacuous."""
+    if guard in ('sub_w_partial', 'sub_w_all'):
+        share = (wq.float().abs() < SUBNORMAL).float().mean().item()
+        assert (share >= 0.10) if guard == 'sub_w_partial' else (share == 1.0), (what, 'subnormal share of the packed weights', share)
+    elif guard == 'sub_x':
+        share = (x.float().abs() < SUBNORMAL).float().mean().item()
+        assert share >= 0.3, (what, 'subnormal share of the activations', share)
+    elif guard == 'saturate':
+        share = (ref.abs() >= HALF_OVER).float().mean().item()
+        assert 0.01 <= share <= 0.5, (what, 'share of saturating outputs', share)
+    else:
+        assert guard is None, guard
 
 
 def kernels_vs_torch(dev):
@@ -134,6 +277,210 @@ def test_half_kernels_on_cpu():
     from hipcpu.host_kernels import host_kernels_abi
     with host_kernels_abi():
         kernels_vs_torch(torch.device('cpu'))
+
+
+# ------------------------------------------------------------------------------------------------ the other entry points, called directly
+def _bits(t):
+    return t.cpu().contiguous().view(torch.int16)
+
+
+def pack_weight_vs_numpy(dev):
+    """rih_hpack_conv_weight bit for bit against numpy: round-to-nearest-even ties (normal and subnormal), clipping to +-65504,
+    with and without a scale, CinPad and Kpad tails zeroed over whatever the buffer held."""
+    import numpy as np
+    from renderih_amd import ops
+    special = [1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, -(1 + 2.0 ** -11), 1 + 2.0 ** -11 + 2.0 ** -20, 2048 + 1, 2048 + 3,    # ties
+               2.0 ** -25, 3 * 2.0 ** -25, -3 * 2.0 ** -25, 2.0 ** -25 * (1 + 2.0 ** -20), 2.0 ** -24, 2.0 ** -14 - 2.0 ** -25,  # subnormals
+               2.0 ** -26, -2.0 ** -30, 0.0, -0.0,
+               65504.0, 65519.0, 65520.0, -65520.0, 1e6, -1e6, 3e38, float('inf'), -float('inf')]                        # clip
+    g = torch.Generator().manual_seed(21)
+    for (Cout, Cin, KH, KW, CinPad, Kpad, with_scale) in [(5, 3, 3, 3, 8, 128, True), (5, 3, 3, 3, 8, 128, False),
+                                                         (3, 8, 1, 1, 8, 64, True), (2, 5, 7, 7, 16, 832, True)]:
+        n = Cout * Cin * KH * KW
+        w = torch.randn(n, generator=g) * torch.pow(10.0, torch.rand(n, generator=g) * 12 - 8)      # 1e-8 .. 1e4
+        w[:min(n, len(special))] = torch.tensor(special[:n])
+        w = w.view(Cout, Cin, KH, KW)
+        scale = torch.tensor([1.0, 0.5, 3.0, 1e-3, -7.0][:Cout]) if with_scale else None
+        dst = torch.full((Cout, Kpad), float('nan'), dtype=F16, device=dev)
+        wd, sd = w.to(dev), None if scale is None else scale.to(dev)
+        rc = ops._L().rih_hpack_conv_weight(wd.data_ptr(), 0 if sd is None else sd.data_ptr(), dst.data_ptr(), Cout, Cin, KH, KW,
+                                            CinPad, Kpad, ops._stream())
+        assert rc == 0
+        with np.errstate(over='ignore'):
+            v = w.numpy() if scale is None else w.numpy() * scale.numpy()[:, None, None, None]      # one fp32 product
+        want = np.zeros((Cout, KH * KW, CinPad), np.float16)
+        want[:, :, :Cin] = np.clip(v, -65504, 65504).astype(np.float16).transpose(0, 2, 3, 1).reshape(Cout, KH * KW, Cin)
+        full = np.zeros((Cout, Kpad), np.float16)
+        full[:, :KH * KW * CinPad] = want.reshape(Cout, -1)
+        assert np.array_equal(_bits(dst).numpy(), full.view(np.int16)), (Cout, Cin, KH, KW, CinPad, Kpad, with_scale)
+
+
+def bn_fold_vs_fp64(dev):
+    """rih_hbn_fold with running_var -> 0 (dead channels: the scale is gamma / sqrt(eps)), with and without a convolution bias and
+    without affine parameters: as close to fp64 as the fp32 torch expression is."""
+    from renderih_amd.testing import assert_fp32_equivalent
+    g = torch.Generator().manual_seed(22)
+    Cn = 70
+    for affine, with_bias in [(True, False), (True, True), (False, True)]:
+        bn = nn.BatchNorm2d(Cn, affine=affine).eval()
+        with torch.no_grad():
+            if affine:
+                bn.weight.copy_(torch.randn(Cn, generator=g) * torch.pow(10.0, torch.rand(Cn, generator=g) * 4 - 4))
+                bn.weight[5] = 0.0
+                bn.bias.copy_(torch.randn(Cn, generator=g))
+            bn.running_mean.copy_(torch.randn(Cn, generator=g))
+            bn.running_var.copy_(torch.pow(10.0, torch.rand(Cn, generator=g) * 13 - 12))             # 1e-12 .. 10
+            bn.running_var[:4] = torch.tensor([0.0, 1e-30, 1e-12, 1e-5])
+        cb = torch.randn(Cn, generator=g) if with_bias else None
+        scale, shift = half.bn_fold(bn.to(dev), None if cb is None else cb.to(dev))
+        gam = bn.weight.detach().cpu() if affine else torch.ones(Cn)
+        bet = bn.bias.detach().cpu() if affine else torch.zeros(Cn)
+        mean, var = bn.running_mean.cpu(), bn.running_var.cpu()
+        s32 = gam / torch.sqrt(var + bn.eps)
+        t32 = bet - mean * s32 + (cb * s32 if cb is not None else 0)
+        s64 = gam.double() / torch.sqrt(var.double() + bn.eps)
+        t64 = bet.double() - mean.double() * s64 + (cb.double() * s64 if cb is not None else 0)
+        print('bn_fold affine=%s bias=%s | scale err / fp32 err %s | shift %s' % (
+            affine, with_bias, assert_fp32_equivalent(scale, s32, s64, what='scale'), assert_fp32_equivalent(shift, t32, t64, what='shift')))
+        # channel by channel too: a dead channel's scale is ~300 x a live one's, a tensor-level bar alone would hide the live ones
+        assert bool(((scale.cpu().double() - s64).abs() <= 4 * 2.0 ** -24 * s64.abs()).all())
+
+
+def image_vs_numpy(dev):
+    """rih_himage_nchw_to_nhwc8 bit for bit: 1, 3 and 8 channels, ties, subnormals, values beyond the fp16 range (saturated)."""
+    import numpy as np
+    special = torch.tensor([1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, -(2048 + 1.0), 2.0 ** -25, 3 * 2.0 ** -25, 2.0 ** -14 - 2.0 ** -25,
+                            65504.0, 65519.0, 65520.0, -65520.0, 1e5, -1e5, 3e38, float('inf'), -float('inf'), 0.0])
+    g = torch.Generator().manual_seed(23)
+    for Cc in (1, 3, 8):
+        img = torch.randn(2, Cc, 5, 7, generator=g) * 3
+        img.view(-1)[:special.numel()] = special
+        img.view(-1)[-special.numel():] = special                 # last image, last channel as well
+        o = half.image_to_nhwc8(img.to(dev)).cpu()
+        want = np.zeros((2, 5, 7, 8), np.float16)
+        want[..., :Cc] = np.clip(img.numpy().transpose(0, 2, 3, 1), -65504, 65504).astype(np.float16)
+        assert np.array_equal(_bits(o).numpy(), want.view(np.int16)), Cc
+
+
+def maxpool_at_edges(dev):
+    """rih_hmaxpool3x3s2 on maps smaller than its window and on all-negative data down to -65504 (a window that starts from 0
+    or from a finite floor instead of -inf shows here): bit-equal."""
+    g = torch.Generator().manual_seed(24)
+    for H in (1, 2, 3):
+        for W in (1, 2, 3):
+            for Cc in (8, 24):
+                x = (-(torch.rand(2, H, W, Cc, generator=g) * 1000 + 1)).to(F16)
+                x[0, 0, 0, :4] = -65504.0
+                x[1, ..., 5] = -65504.0                         # a whole channel at the floor
+                ref = F.max_pool2d(x.float().permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1).to(F16)
+                assert torch.equal(half.maxpool3x3s2(x.to(dev)).cpu(), ref), (H, W, Cc)
+
+
+def upsample_at_edges(dev):
+    """rih_hupsample2x on one-row / one-column maps (the align_corners scale is 0 there): within one fp16 step of fp64."""
+    g = torch.Generator().manual_seed(25)
+    for (N, H, W, Cc) in [(1, 1, 1, 8), (2, 1, 5, 8), (1, 4, 1, 16), (1, 2, 2, 8)]:
+        x = (torch.randn(N, H, W, Cc, generator=g) * 10).to(F16)
+        ref = F.interpolate(x.double().permute(0, 3, 1, 2), scale_factor=2, mode='bilinear', align_corners=True).permute(0, 2, 3, 1)
+        got = half.upsample2x(x.to(dev)).cpu().double()
+        assert got.shape == ref.shape
+        steps = ((got - ref).abs() / half_step(ref.abs().clamp_min(2.0 ** -24))).max().item()
+        print('upsample2x %s | worst %.3g fp16 steps from fp64' % ((N, H, W, Cc), steps))
+        assert steps <= 1.0, ((N, H, W, Cc), steps)
+
+
+def avgpool_at_edges(dev):
+    """rih_havgpool on one pixel, on 4096 pixels around a mean of 5 (the running sum reaches 2e4: fp32 accumulation is what keeps
+    the mean), 8 and 72 channels read from a slice of a wider tensor: as close to fp64 as torch's fp32 mean."""
+    from renderih_amd.testing import assert_fp32_equivalent
+    g = torch.Generator().manual_seed(26)
+    for (N, H, W, Cc, pitch) in [(2, 1, 1, 8, 0), (1, 1, 1, 72, 8), (1, 64, 64, 8, 16), (2, 64, 64, 72, 8)]:
+        xw = (torch.randn(N, H, W, Cc + pitch, generator=g) + 5).to(F16)
+        got = half.global_avgpool(xw.to(dev)[..., pitch:])
+        x = xw[..., pitch:]
+        r = assert_fp32_equivalent(got, x.float().mean(dim=(1, 2)), x.double().mean(dim=(1, 2)), what=str((N, H, W, Cc)))
+        print('avgpool %s | err vs fp64 %.3g, torch fp32 %.3g' % ((N, H, W, Cc, pitch), r[0], r[1]))
+
+
+ENTRY_POINTS = {'hpack_conv_weight': pack_weight_vs_numpy, 'hbn_fold': bn_fold_vs_fp64, 'himage': image_vs_numpy,
+                'hmaxpool': maxpool_at_edges, 'hupsample2x': upsample_at_edges, 'havgpool': avgpool_at_edges}
+
+
+@pytest.mark.parametrize('abi', ['host_kernels', 'emulated'])
+@pytest.mark.parametrize('entry', sorted(ENTRY_POINTS))
+def test_half_entry_points_on_cpu(entry, abi):
+    from abi_emulator import emulated_abi
+    from hipcpu.host_kernels import host_kernels_abi
+    with (host_kernels_abi if abi == 'host_kernels' else emulated_abi)():
+        ENTRY_POINTS[entry](torch.device('cpu'))
+
+
+import half_cases          # noqa: E402
+
+
+@pytest.mark.parametrize('kernel,regime', half_cases.CASES, ids=lambda v: v)
+def test_half_range_on_cpu(kernel, regime):
+    """tests/half_cases.py on the host build of the kernels: each convolution kernel under each off-unit-scale regime."""
+    from hipcpu.host_kernels import host_kernels_abi
+    with host_kernels_abi():
+        half_cases.run_case(conv_case, torch.device('cpu'), kernel, regime)
+
+
+@pytest.mark.parametrize('kernel,regime', half_cases.CASES, ids=lambda v: v)
+def test_half_range_emulated(kernel, regime):
+    """The same list through the numpy / torch restatement of the entry points: its kernel choice (rih_hconv_plan) and its
+    rounding and saturation points are the kernels'."""
+    from abi_emulator import emulated_abi
+    with emulated_abi():
+        half_cases.run_case(conv_case, torch.device('cpu'), kernel, regime)
+
+
+def test_half_case_plans_cover_every_instantiation():
+    """Every hconv_kernel<BN, GLDS> and hconv3_halo_kernel<TW, BN> is the expected plan of some case of tests/half_cases.py
+    under the default switches or one of the three child interpreters of tests/test_gpu_half_range.py."""
+    B_, HALO, TW16, BN128, REGS = half.PLAN_BASE, half.PLAN_HALO, half.PLAN_TW16, half.PLAN_BN128, half.PLAN_REGS
+    every = {B_ | bn | regs for bn in (0, BN128) for regs in (0, REGS)} | {B_ | HALO | tw | bn for tw in (0, TW16) for bn in (0, BN128)}
+    named = {p for table in (half_cases.KERNELS, half_cases.WIDE) for v in table.values() for p in v[3]}
+    assert every <= named, sorted(hex(p) for p in every - named)
+
+
+def test_half_plan_refuses_what_hconv_refuses():
+    """rih_hconv_plan is negative exactly where rih_hconv returns an error (one helper decides for both)."""
+    import ctypes as C
+    from abi_emulator import emulated_abi
+    from hipcpu.host_kernels import host_kernels_abi
+    from renderih_amd import ops
+    spoil = [('Kpad', 65), ('Kpad', 0), ('ldx', 60), ('Cin', 12), ('ldy', 8), ('Ho', 5), ('stride', 0), ('zero', None), ('post_shift', None)]
+    for abi in (host_kernels_abi, emulated_abi):
+        with abi():
+            pc = half.PackedConv(nn.Conv2d(64, 64, 3, 1, 1, bias=False), nn.BatchNorm2d(64).eval(), 'conv-relu-bn')
+            x = torch.zeros(1, 8, 32, 64, dtype=F16)
+            assert pc.plan(x) == half.PLAN_BASE | half.PLAN_HALO
+            for field, value in spoil:
+                d, out = pc._desc(x, False, None, None, False)
+                setattr(d, field, value)
+                assert ops._L().rih_hconv_plan(C.byref(d)) < 0, field
+                if abi is host_kernels_abi:
+                    assert ops._L().rih_hconv(C.byref(d), 0) < 0, field
+
+
+@pytest.mark.parametrize('kernel', list(half_cases.WIDE))
+def test_half_wide_tile_plans(kernel):
+    """The 128-channel halo tiles are picked by workgroup count: the plan of each wide shape, and of the shape one step below the
+    rule, from the host build and from the emulator (nothing is launched)."""
+    from abi_emulator import emulated_abi
+    from hipcpu.host_kernels import host_kernels_abi
+    for abi in (host_kernels_abi, emulated_abi):
+        with abi():
+            half_cases.run_case(conv_case, torch.device('cpu'), kernel, 'unit', run=False)
+
+
+@pytest.mark.skipif(os.environ.get('HIPCPU_MORE', '0') != '1', reason='256 workgroups each on the fiber harness: run with HIPCPU_MORE=1')
+@pytest.mark.parametrize('kernel,regime', half_cases.WIDE_CASES, ids=lambda v: v)
+def test_half_wide_tiles_on_cpu(kernel, regime):
+    from hipcpu.host_kernels import host_kernels_abi
+    with host_kernels_abi():
+        half_cases.run_case(conv_case, torch.device('cpu'), kernel, regime)
 
 
 def test_half_kernels_register_staging_on_cpu():
@@ -237,6 +584,118 @@ def test_half_backbone_kernels_on_cpu():
     from hipcpu.host_kernels import host_kernels_abi
     with host_kernels_abi():
         backbone_vs_fp32(torch.device('cpu'), size=32, through_decoder=False)
+
+
+# ------------------------------------------------------------------------------------------------ checkpoint-like BatchNorm statistics
+def checkpoint_like_model(seed=3):
+    """tiny_model with the BatchNorm statistics of a trained checkpoint instead of unit-scale ones: weights log-uniform in
+    [1e-4, 2], running variances log-uniform in [1e-6, 10] (dead channels), three weights per layer exactly 0.  As in a trained
+    network the statistics describe what the convolution in front of them produces: its output channels (and the running
+    mean) are scaled by sqrt(var), so the activations stay in range while the folded scales gamma / sqrt(var + eps) span
+    seven decades."""
+    import math
+    m = tiny_model(seed)
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for part in (m.encoder, m.mid_model):
+            conv = None
+            for mod in part.modules():                # registration order: a BatchNorm follows the convolution it normalises
+                if isinstance(mod, nn.Conv2d):
+                    conv = mod
+                elif isinstance(mod, nn.BatchNorm2d):
+                    Cn = mod.num_features
+                    assert conv is not None and conv.out_channels == Cn
+                    mod.weight.copy_(torch.exp(math.log(1e-4) + torch.rand(Cn, generator=g) * (math.log(2.0) - math.log(1e-4))))
+                    var = torch.pow(10.0, torch.rand(Cn, generator=g) * 7 - 6)
+                    sd = torch.sqrt(var / mod.running_var)
+                    conv.weight.mul_(sd[:, None, None, None])
+                    if conv.bias is not None:
+                        conv.bias.mul_(sd)
+                    mod.running_mean.mul_(sd)
+                    mod.running_var.copy_(var)
+                    mod.weight[torch.randperm(Cn, generator=g)[:3]] = 0.0
+                    conv = None
+    return m
+
+
+def checkpoint_like_image(size=32):
+    from renderih_amd import testing
+    return testing.seeded_image(1, 7)[..., :size, :size].contiguous()
+
+
+def backbone_outputs(m, img):
+    """Every tensor HalfBackbone hands to the decoder, by name, on the CPU."""
+    with torch.no_grad():
+        hms, mask, dp, gf, fmaps = half.HalfBackbone(m.encoder, m.mid_model)(img)
+    out = {'hms': hms, 'mask': mask, 'dp': dp, 'gf': gf}
+    out.update(('fmap%d' % i, f) for i, f in enumerate(fmaps))
+    return {k: v.detach().cpu() for k, v in out.items()}
+
+
+def fp32_outputs(m, img):
+    with torch.no_grad():
+        hms, mask, dp, img_fmaps, hms_fmaps, dp_fmaps = m.encoder(img)
+        gf, fmaps = m.mid_model(img_fmaps, hms_fmaps, dp_fmaps)
+    out = {'hms': hms, 'mask': mask, 'dp': dp, 'gf': gf}
+    out.update(('fmap%d' % i, f) for i, f in enumerate(fmaps))
+    return out
+
+
+def _rel(a, b):
+    from renderih_amd import testing
+    return testing.rel_err(a, b)
+
+
+# HalfBackbone on the host build of the kernels against HalfBackbone on the emulator, checkpoint_like_model(3) on a 32 x 32 image:
+# the largest max|a - b| / max|b| over the tensors handed to the decoder (profiles/half_range/README.md).  The two round at
+# the same points -- fp16 storage after every layer, fp32 epilogues -- and differ only in the order of the fp32 sums.
+HOST_VS_EMULATOR = 1.26e-4
+
+
+def backbone_kernels_vs_emulator(dev, kernels_abi, bar, size=32):
+    """HalfBackbone through the kernels (`kernels_abi`: a context manager, or None on the GPU) against the same HalfBackbone
+    through tests/abi_emulator.py on the CPU.  Returns {tensor: (deviation from the emulator, the emulator's deviation from the
+    fp32 modules)}; the first is asserted against `bar`, the second only recorded."""
+    import contextlib
+    from abi_emulator import emulated_abi
+    m = checkpoint_like_model(3)
+    img = checkpoint_like_image(size)
+    with emulated_abi():
+        want = backbone_outputs(m, img)
+        f32 = fp32_outputs(m, img)
+    m = m.to(dev)
+    with (kernels_abi() if kernels_abi is not None else contextlib.nullcontext()):
+        got = backbone_outputs(m, img.to(dev))
+    worst = {}
+    for k in want:
+        assert got[k].shape == want[k].shape and bool(torch.isfinite(got[k]).all()), k
+        worst[k] = (_rel(got[k], want[k]), _rel(want[k], f32[k]))
+        print('half_backbone checkpoint-like %s | kernels vs emulator %.3g | emulator vs fp32 modules %.3g (not asserted) | max %.3g'
+              % (k, worst[k][0], worst[k][1], want[k].abs().max()))
+    if bar is not None:
+        assert max(v[0] for v in worst.values()) <= bar, (bar, worst)
+    return worst
+
+
+@pytest.mark.skipif(os.environ.get('HIPCPU_MORE', '0') != '1', reason='4 min on the fiber harness: run with HIPCPU_MORE=1')
+def test_half_backbone_checkpoint_like_on_cpu():
+    """The measurement behind HOST_VS_EMULATOR, repeated: the host build of the kernels against the emulator."""
+    from hipcpu.host_kernels import host_kernels_abi
+    backbone_kernels_vs_emulator(torch.device('cpu'), host_kernels_abi, bar=HOST_VS_EMULATOR)
+
+
+def test_half_backbone_checkpoint_like_statistics_are_wide():
+    """checkpoint_like_model is what it says: folded scales over more than five decades, exact zeros among them, and the
+    emulated fp16 backbone still within 1e-2 of the fp32 modules (the bar of backbone_vs_fp32), so nothing has saturated."""
+    from abi_emulator import emulated_abi
+    m = checkpoint_like_model(3)
+    s = torch.cat([(b.weight / torch.sqrt(b.running_var + b.eps)).detach() for b in m.encoder.modules() if isinstance(b, nn.BatchNorm2d)])
+    assert bool((s == 0).any()) and (s.max() / s[s > 0].min()).item() > 1e5
+    img = checkpoint_like_image(32)
+    with emulated_abi():
+        got, want = backbone_outputs(m, img), fp32_outputs(m, img)
+    for k in got:
+        assert _rel(got[k], want[k]) < 1e-2, k
 
 
 def test_half_backbone_requires_eval():
