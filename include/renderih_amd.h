@@ -377,6 +377,31 @@ int rih_bn_bwd(const float* dy, const float* x, const float* y, const float* mea
                int relu, int frozen_stats, float* ws, const uint8_t* relu_mask, float* amax_dx, void* stream);
 /* amax_dx (optional, ABI 13): a bound block that receives max|dx|, as `amax` of rih_bn_apply -- dx is the gradient operand of
  * the producing convolution's data- and weight-gradient GEMMs. */
+/* BatchNorm pairs (ABI 30): y = act(BN_a(xa) + BN_b(xb)), the end of a residual block whose skip branch ends in a BatchNorm of
+ * its own (torchvision Bottleneck.downsample).  rih_bn_apply2 leaves in y, relu_mask and amax exactly what
+ * rih_bn_apply(xb, .., residual = NULL, relu = 0) followed by rih_bn_apply(xa, .., residual = that output, relu) leaves, without
+ * the branch's output in memory.  rih_bn_bwd2 leaves in dxa, dxb, dgamma_*, dbeta_* and the two bound blocks exactly what
+ * rih_bn_bwd(dy, xa, .., dres, relu, frozen_a, relu_mask) followed by rih_bn_bwd(dres, xb, .., relu = 0, frozen_b) leaves, without
+ * dres in memory: one reduction pass with three sums (dbeta_a == dbeta_b), one apply pass with two outputs.  relu != 0 needs
+ * relu_mask.  ws: >= rih_bn_ws2_floats(rows, C) floats. */
+/* BatchNorm -> ReLU -> max-pool 3x3/2 (ABI 30; the ResNet stem, x: [N][H][W][C]): rih_bn_pool_fwd leaves in y_pooled, arg and amax
+ * exactly what rih_bn_apply(relu = 1) followed by rih_maxpool3x3s2_fwd leaves (amax: max|y_pooled| = max|y|, every element of y
+ * >= 0 lies in some window), rih_bn_pool_bwd in dx, dgamma, dbeta and amax_dx exactly what rih_maxpool3x3s2_bwd followed by
+ * rih_bn_bwd(relu = 1) leaves; neither full-resolution intermediate is stored and no ReLU mask is needed (the sign of the
+ * recomputed bn(x) gates).  Pointers 16-byte aligned, C % 4 == 0; ws: >= rih_bn_ws_floats(N*H*W, C) floats. */
+int rih_bn_pool_fwd(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                    float* y_pooled, int8_t* arg, int N, int H, int W, int C, float* amax, void* stream);
+int rih_bn_pool_bwd(const float* dy_pooled, const int8_t* arg, const float* x, const float* mean, const float* invstd,
+                    const float* gamma, const float* beta, float* dx, float* dgamma, float* dbeta, int N, int H, int W, int C,
+                    int frozen_stats, float* ws, float* amax_dx, void* stream);
+int64_t rih_bn_ws2_floats(int rows, int C);
+int rih_bn_apply2(const float* xa, const float* mean_a, const float* invstd_a, const float* gamma_a, const float* beta_a,
+                  const float* xb, const float* mean_b, const float* invstd_b, const float* gamma_b, const float* beta_b,
+                  float* y, int rows, int C, int relu, uint8_t* relu_mask, float* amax, void* stream);
+int rih_bn_bwd2(const float* dy, const float* xa, const float* mean_a, const float* invstd_a, const float* gamma_a,
+                const float* xb, const float* mean_b, const float* invstd_b, const float* gamma_b, float* dxa, float* dxb,
+                float* dgamma_a, float* dbeta_a, float* dgamma_b, float* dbeta_b, int rows, int C, int relu, int frozen_a,
+                int frozen_b, float* ws, const uint8_t* relu_mask, float* amax_dxa, float* amax_dxb, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Row-wise ops on [rows][D] matrices (decoder)                                                         */
@@ -735,7 +760,7 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc, opt state, adam dev entry (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 29
+#define RIH_ABI_VERSION 30
 #define RIH_ABI_NSIZES 14
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);

@@ -188,6 +188,11 @@ SIGNATURES = {
     'rih_bn_eval_stats': (c_i, [c_f, c_f, c_i, c_fl, c_f, c_f, C.c_void_p]),
     'rih_bn_apply': (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, C.c_void_p, c_f, C.c_void_p]),
     'rih_bn_bwd': (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, C.c_void_p, c_f, C.c_void_p]),
+    'rih_bn_pool_fwd': (c_i, [c_f] * 7 + [c_i, c_i, c_i, c_i, c_f, C.c_void_p]),
+    'rih_bn_pool_bwd': (c_i, [c_f] * 10 + [c_i, c_i, c_i, c_i, c_i, c_f, c_f, C.c_void_p]),
+    'rih_bn_ws2_floats': (c_l, [c_i, c_i]),
+    'rih_bn_apply2': (c_i, [c_f] * 11 + [c_i, c_i, c_i, C.c_void_p, c_f, C.c_void_p]),
+    'rih_bn_bwd2': (c_i, [c_f] * 15 + [c_i, c_i, c_i, c_i, c_i, c_f, C.c_void_p, c_f, c_f, C.c_void_p]),
     'rih_layernorm_fwd': (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_fl, c_i, C.c_void_p]),
     'rih_ln_nblk': (c_i, [c_i]),
     'rih_layernorm_fwd_grouped': (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_l, c_l, c_fl, c_i, C.c_void_p]),
@@ -263,7 +268,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 29     # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 30    # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 

@@ -497,6 +497,17 @@ __global__ void bn_eval_stats_kernel(const float* __restrict__ rmean, const floa
     invstd[c] = 1.f / sqrtf(rvar[c] + eps);
 }
 
+// gamma * (x - mean) * invstd + beta of one quad: the one expression every kernel that applies a BatchNorm shares (bn_apply_kernel,
+// bn_apply2_kernel), so that the compiler contracts it into the same FMAs in each of them
+__device__ __forceinline__ float4 bn_affine(const float4 v, const float4 m, const float4 is, const float4 ga, const float4 be) {
+    float4 o;
+    o.x = (v.x - m.x) * (is.x * ga.x) + be.x;
+    o.y = (v.y - m.y) * (is.y * ga.y) + be.y;
+    o.z = (v.z - m.z) * (is.z * ga.z) + be.z;
+    o.w = (v.w - m.w) * (is.w * ga.w) + be.w;
+    return o;
+}
+
 __global__ void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                 const float* __restrict__ invstd, const float* __restrict__ gamma,
                                 const float* __restrict__ beta, const float* __restrict__ res, float* __restrict__ y,
@@ -511,11 +522,7 @@ __global__ void bn_apply_kernel(const float* __restrict__ x, const float* __rest
         const float4 is = reinterpret_cast<const float4*>(invstd)[g];
         const float4 ga = reinterpret_cast<const float4*>(gamma)[g];
         const float4 be = reinterpret_cast<const float4*>(beta)[g];
-        float4 o;
-        o.x = (v.x - m.x) * (is.x * ga.x) + be.x;
-        o.y = (v.y - m.y) * (is.y * ga.y) + be.y;
-        o.z = (v.z - m.z) * (is.z * ga.z) + be.z;
-        o.w = (v.w - m.w) * (is.w * ga.w) + be.w;
+        float4 o = bn_affine(v, m, is, ga, be);
         if (res != nullptr) {
             const float4 r = reinterpret_cast<const float4*>(res)[i];
             o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
@@ -660,6 +667,398 @@ __global__ void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* _
         }
         reinterpret_cast<float4*>(dx)[i] = o;
         am = fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+    }
+    if (amax != nullptr) amax_publish(amax, am);
+}
+
+// ------------------------------------------------------------------------------------------------ BatchNorm pairs
+// y = act(BN_a(xa) + BN_b(xb)): the last BatchNorm of a residual block whose skip branch ends in a BatchNorm of its own
+// (Bottleneck.downsample).  As two rih_bn_apply calls the branch's output is written once and read once, and in the backward the
+// gated dy (`dres`) is written once and read twice, for nothing: nobody else reads either.  The kernels below form both in
+// registers; every output is bit for bit what rih_bn_apply(b) -> rih_bn_apply(a, residual) and rih_bn_bwd(a, dres) ->
+// rih_bn_bwd(b, dy = dres) leave (tests/test_gpu_bn_fuse.py), because every sum keeps its geometry and its order (col_geom, the
+// rows of a thread in increasing order, block_col_reduce, one wavefront per channel in fp64) and every expression its shape.
+__global__ void bn_apply2_kernel(const float* __restrict__ xa, const float* __restrict__ mean_a,
+                                 const float* __restrict__ invstd_a, const float* __restrict__ gamma_a,
+                                 const float* __restrict__ beta_a, const float* __restrict__ xb,
+                                 const float* __restrict__ mean_b, const float* __restrict__ invstd_b,
+                                 const float* __restrict__ gamma_b, const float* __restrict__ beta_b, float* __restrict__ y,
+                                 long long nquads, int C, int relu, unsigned char* __restrict__ mask,
+                                 float* __restrict__ amax) {
+    const int CG = C / 4;
+    float am = 0.f;
+    GRID_STRIDE(i, nquads) {
+        const int g = (int)(i % CG);
+        const float4 va = reinterpret_cast<const float4*>(xa)[i];
+        const float4 vb = reinterpret_cast<const float4*>(xb)[i];
+        const float4 r = bn_affine(vb, reinterpret_cast<const float4*>(mean_b)[g], reinterpret_cast<const float4*>(invstd_b)[g],
+                                   reinterpret_cast<const float4*>(gamma_b)[g], reinterpret_cast<const float4*>(beta_b)[g]);
+        float4 o = bn_affine(va, reinterpret_cast<const float4*>(mean_a)[g], reinterpret_cast<const float4*>(invstd_a)[g],
+                             reinterpret_cast<const float4*>(gamma_a)[g], reinterpret_cast<const float4*>(beta_a)[g]);
+        o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
+        if (relu) {
+            if (mask != nullptr)
+                mask[i] = (unsigned char)((o.x > 0.f ? 1 : 0) | (o.y > 0.f ? 2 : 0) | (o.z > 0.f ? 4 : 0) | (o.w > 0.f ? 8 : 0));
+            o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
+        }
+        reinterpret_cast<float4*>(y)[i] = o;
+        am = fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+    }
+    if (amax != nullptr) amax_publish(amax, am);
+}
+
+// dy of one quad as the BatchNorm behind a ReLU sees it: from memory, zeroed where the sign byte of the forward says y <= 0
+// (mask == nullptr: no ReLU)
+struct GatedDy {
+    const float* __restrict__ dy;
+    const unsigned char* __restrict__ mask;
+    struct Raw {
+        float4 d;
+        unsigned bits;
+    };
+    __device__ __forceinline__ Raw load(int, int, long long quad) const {
+        Raw w;
+        w.d = reinterpret_cast<const float4*>(dy)[quad];
+        w.bits = mask != nullptr ? mask[quad] : 15u;
+        return w;
+    }
+    __device__ __forceinline__ float4 gate(Raw w, const float4) const {
+        if (!(w.bits & 1u)) w.d.x = 0.f;
+        if (!(w.bits & 2u)) w.d.y = 0.f;
+        if (!(w.bits & 4u)) w.d.z = 0.f;
+        if (!(w.bits & 8u)) w.d.w = 0.f;
+        return w.d;
+    }
+};
+struct BnSide {     // one BatchNorm of a fused backward: its input and its statistics
+    const float* __restrict__ x;
+    const float* __restrict__ mean;
+    const float* __restrict__ invstd;
+};
+
+// Backward pass 1 over NX BatchNorms that share one dy: ws[0] = sum d per chunk, ws[1 + k] = sum d * xhat_k.  The geometry and
+// the order of bn_bwd_partial_kernel (rih_bn_bwd_partial.inc), sum for sum: U rows per iteration with all their loads in
+// flight, accumulated in row order (how many rows are in flight changes no sum: every thread adds its rows one after the other).
+template <int NX, int U, bool AHEAD, class Src>
+__device__ __forceinline__ void bn_bwd_partial_body(const Src src, const BnSide (&in)[NX], int rows, int C, int cgb, int rt,
+                                                    int rows_per_chunk, float* __restrict__ ws) {
+    const int cg = threadIdx.x % cgb, ry = threadIdx.x / cgb;
+    const int g = blockIdx.x * cgb + cg;
+    const int CG = C / 4;
+    const int chunk = blockIdx.y, nchunk = gridDim.y;
+    float4 acc[1 + NX];
+#pragma unroll
+    for (int k = 0; k <= NX; ++k) acc[k] = make_float4(0, 0, 0, 0);
+    if (g < CG) {
+        float4 m[NX], is[NX];
+#pragma unroll
+        for (int k = 0; k < NX; ++k) {
+            m[k] = reinterpret_cast<const float4*>(in[k].mean)[g];
+            is[k] = reinterpret_cast<const float4*>(in[k].invstd)[g];
+        }
+        const int r0 = chunk * rows_per_chunk, r1 = min(rows, r0 + rows_per_chunk);
+        auto add = [&](const float4 d, const float4 (&v)[NX]) {
+            acc[0].x += d.x; acc[0].y += d.y; acc[0].z += d.z; acc[0].w += d.w;
+#pragma unroll
+            for (int k = 0; k < NX; ++k) {
+                acc[1 + k].x += d.x * ((v[k].x - m[k].x) * is[k].x);
+                acc[1 + k].y += d.y * ((v[k].y - m[k].y) * is[k].y);
+                acc[1 + k].z += d.z * ((v[k].z - m[k].z) * is[k].z);
+                acc[1 + k].w += d.w * ((v[k].w - m[k].w) * is[k].w);
+            }
+        };
+        struct Stage {      // U rows of this thread with every load of theirs issued
+            typename Src::Raw w[U];
+            float4 v[U][NX];
+        };
+        auto fetch = [&](Stage& st, int r) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const long long q = (long long)(r + u * rt) * CG + g;
+                st.w[u] = src.load(r + u * rt, g, q);
+#pragma unroll
+                for (int k = 0; k < NX; ++k) st.v[u][k] = reinterpret_cast<const float4*>(in[k].x)[q];
+            }
+        };
+        auto consume = [&](const Stage& st) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) add(src.gate(st.w[u], st.v[u][0]), st.v[u]);
+        };
+        int r = r0 + ry;
+        if constexpr (AHEAD) {
+            // the next U rows are requested before this stage's arithmetic: a source whose gate is long (PooledDy) on a grid of
+            // one wavefront per SIMD otherwise alternates between waiting for memory and computing
+            if (r + (U - 1) * rt < r1) {
+                Stage cur;
+                fetch(cur, r);
+                for (r += U * rt; r + (U - 1) * rt < r1; r += U * rt) {
+                    Stage nxt;
+                    fetch(nxt, r);
+                    consume(cur);
+                    cur = nxt;
+                }
+                consume(cur);
+            }
+        } else {
+            for (; r + (U - 1) * rt < r1; r += U * rt) {
+                Stage st;
+                fetch(st, r);
+                consume(st);
+            }
+        }
+        for (; r < r1; r += rt) {
+            const long long q = (long long)r * CG + g;
+            const typename Src::Raw w = src.load(r, g, q);
+            float4 v[NX];
+#pragma unroll
+            for (int k = 0; k < NX; ++k) v[k] = reinterpret_cast<const float4*>(in[k].x)[q];
+            add(src.gate(w, v[0]), v);
+        }
+    }
+    block_col_reduce<1 + NX>(acc, cg, ry, cgb, rt);
+    if (ry == 0 && g < CG) {
+#pragma unroll
+        for (int k = 0; k <= NX; ++k) *reinterpret_cast<float4*>(ws + ((long long)k * nchunk + chunk) * C + g * 4) = acc[k];
+    }
+}
+__global__ __launch_bounds__(TPB) void bn_bwd2_partial_kernel(const GatedDy src, const BnSide a, const BnSide b, int rows, int C,
+                                                              int cgb, int rt, int rows_per_chunk, float* __restrict__ ws) {
+    const BnSide in[2] = {a, b};
+    bn_bwd_partial_body<2, 4, false>(src, in, rows, C, cgb, rt, rows_per_chunk, ws);
+}
+
+// two_sum_final_kernel with a third plane: sum d (both dbeta: the branch's dy is the gated dy), sum d*xhat_a, sum d*xhat_b
+__global__ __launch_bounds__(TPB) void three_sum_final_kernel(const float* __restrict__ ws, int C, int nchunk,
+                                                              float* __restrict__ out0a, float* __restrict__ out0b,
+                                                              float* __restrict__ out1, float* __restrict__ out2) {
+    const int lane = threadIdx.x & 63;
+    const int c = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
+    if (c >= C) return;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int k = lane; k < nchunk; k += 64) {
+        s0 += (double)ws[((long long)0 * nchunk + k) * C + c];
+        s1 += (double)ws[((long long)1 * nchunk + k) * C + c];
+        s2 += (double)ws[((long long)2 * nchunk + k) * C + c];
+    }
+    s0 = wave_sum_d(s0);
+    s1 = wave_sum_d(s1);
+    s2 = wave_sum_d(s2);
+    if (lane == 0) { out0a[c] = (float)s0; out0b[c] = (float)s0; out1[c] = (float)s1; out2[c] = (float)s2; }
+}
+
+// dx of one quad: the two formulas of bn_bwd_apply_kernel (`frozen` as there; v is read only where they need it)
+__device__ __forceinline__ float4 bn_bwd_dx(const float4 d, const float* __restrict__ x, long long i, const float4 m,
+                                            const float4 is, const float4 ga, const float4 s1, const float4 s2,
+                                            float inv_rows, int frozen) {
+    const bool in_relu = (frozen & 2) != 0;
+    float4 o;
+    if (frozen & 1) {
+        o.x = d.x * is.x * ga.x; o.y = d.y * is.y * ga.y; o.z = d.z * is.z * ga.z; o.w = d.w * is.w * ga.w;
+        if (in_relu) {
+            const float4 v = reinterpret_cast<const float4*>(x)[i];
+            if (!(v.x > 0.f)) o.x = 0.f;
+            if (!(v.y > 0.f)) o.y = 0.f;
+            if (!(v.z > 0.f)) o.z = 0.f;
+            if (!(v.w > 0.f)) o.w = 0.f;
+        }
+    } else {
+        const float4 v = reinterpret_cast<const float4*>(x)[i];
+        o.x = (d.x - s1.x * inv_rows - ((v.x - m.x) * is.x) * (s2.x * inv_rows)) * (is.x * ga.x);
+        o.y = (d.y - s1.y * inv_rows - ((v.y - m.y) * is.y) * (s2.y * inv_rows)) * (is.y * ga.y);
+        o.z = (d.z - s1.z * inv_rows - ((v.z - m.z) * is.z) * (s2.z * inv_rows)) * (is.z * ga.z);
+        o.w = (d.w - s1.w * inv_rows - ((v.w - m.w) * is.w) * (s2.w * inv_rows)) * (is.w * ga.w);
+        if (in_relu) {
+            if (!(v.x > 0.f)) o.x = 0.f;
+            if (!(v.y > 0.f)) o.y = 0.f;
+            if (!(v.z > 0.f)) o.z = 0.f;
+            if (!(v.w > 0.f)) o.w = 0.f;
+        }
+    }
+    return o;
+}
+__device__ __forceinline__ float f4absmax(float am, const float4 o) {
+    return fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+}
+
+__global__ void bn_bwd2_apply_kernel(const GatedDy src, const BnSide a, const float* __restrict__ gamma_a, const BnSide b,
+                                     const float* __restrict__ gamma_b, const float* __restrict__ sum_dy,
+                                     const float* __restrict__ sum_dyxh_a, const float* __restrict__ sum_dyxh_b,
+                                     float* __restrict__ dxa, float* __restrict__ dxb, long long nquads, int C,
+                                     float inv_rows, int frozen_a, int frozen_b, float* __restrict__ amax_a,
+                                     float* __restrict__ amax_b) {
+    const int CG = C / 4;
+    float ama = 0.f, amb = 0.f;
+    GRID_STRIDE(i, nquads) {
+        const int g = (int)(i % CG);
+        const float4 d = src.gate(src.load(0, 0, i), make_float4(0, 0, 0, 0));
+        const float4 s1 = reinterpret_cast<const float4*>(sum_dy)[g];
+        const float4 oa = bn_bwd_dx(d, a.x, i, reinterpret_cast<const float4*>(a.mean)[g],
+                                    reinterpret_cast<const float4*>(a.invstd)[g], reinterpret_cast<const float4*>(gamma_a)[g], s1,
+                                    reinterpret_cast<const float4*>(sum_dyxh_a)[g], inv_rows, frozen_a);
+        const float4 ob = bn_bwd_dx(d, b.x, i, reinterpret_cast<const float4*>(b.mean)[g],
+                                    reinterpret_cast<const float4*>(b.invstd)[g], reinterpret_cast<const float4*>(gamma_b)[g], s1,
+                                    reinterpret_cast<const float4*>(sum_dyxh_b)[g], inv_rows, frozen_b);
+        reinterpret_cast<float4*>(dxa)[i] = oa;
+        reinterpret_cast<float4*>(dxb)[i] = ob;
+        ama = f4absmax(ama, oa);
+        amb = f4absmax(amb, ob);
+    }
+    if (amax_a != nullptr) amax_publish(amax_a, ama);
+    __syncthreads();        // amax_publish's staging words are one array: the second call must not overwrite it under the first's reader
+    if (amax_b != nullptr) amax_publish(amax_b, amb);
+}
+
+// ------------------------------------------------------------------------------------------------ BatchNorm -> ReLU -> max-pool
+// The ResNet stem: the BatchNorm's output has one reader, the 3x3/2 max-pool, and the pool's input gradient one, the BatchNorm's
+// backward.  Fused, neither full-resolution tensor exists: the forward pools relu(bn(x)) over its nine taps in registers, the
+// backward gathers the gradient of a full-resolution quad from its <= 4 covering windows.  Same results as rih_bn_apply ->
+// rih_maxpool3x3s2_fwd and rih_maxpool3x3s2_bwd -> rih_bn_bwd, bit for bit (tests/test_gpu_bn_fuse.py): the pooling rules
+// (first maximum in (kh, kw) order, NaN wins, taps outside the map skipped), the gather's order (ho, then wo, s += d) and the
+// sums' geometry are those of maxpool_fwd_kernel, maxpool_bwd_kernel and bn_bwd_partial_kernel.
+__global__ void bn_pool_fwd_kernel(const float* __restrict__ x, const float* __restrict__ mean,
+                                   const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                   const float* __restrict__ beta, float* __restrict__ y, unsigned* __restrict__ arg, int N, int H,
+                                   int W, int C, int Ho, int Wo, float* __restrict__ amax) {
+    const int CG = C / 4;
+    const long long total = (long long)N * Ho * Wo * CG;
+    float am = 0.f;
+    GRID_STRIDE(i, total) {
+        const int g = (int)(i % CG);
+        long long t = i / CG;
+        const int wo = (int)(t % Wo);
+        t /= Wo;
+        const int ho = (int)(t % Ho);
+        const int n = (int)(t / Ho);
+        float4 v[9];
+        bool ok[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {           // the nine taps in flight before the first is used
+            const int hi = ho * 2 - 1 + k / 3, wi = wo * 2 - 1 + k % 3;
+            ok[k] = hi >= 0 && hi < H && wi >= 0 && wi < W;
+            // a tap outside the map reads the centre tap (always inside) and is skipped below: no load behind a branch
+            v[k] = reinterpret_cast<const float4*>(x)[(((long long)n * H + (ok[k] ? hi : ho * 2)) * W + (ok[k] ? wi : wo * 2)) * CG + g];
+        }
+        const float4 m = reinterpret_cast<const float4*>(mean)[g];
+        const float4 is = reinterpret_cast<const float4*>(invstd)[g];
+        const float4 ga = reinterpret_cast<const float4*>(gamma)[g];
+        const float4 be = reinterpret_cast<const float4*>(beta)[g];
+        float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+        unsigned bi = 0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            if (!ok[k]) continue;
+            const float4 o = bn_affine(v[k], m, is, ga, be);
+            const float pv[4] = {fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f)};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (pv[e] > best[e] || pv[e] != pv[e]) { best[e] = pv[e]; bi = (bi & ~(0xffu << (8 * e))) | ((unsigned)k << (8 * e)); }
+        }
+        const float4 b4 = make_float4(best[0], best[1], best[2], best[3]);
+        reinterpret_cast<float4*>(y)[i] = b4;
+        arg[i] = bi;
+        am = f4absmax(am, b4);
+    }
+    if (amax != nullptr) amax_publish(amax, am);
+}
+
+// The gated gradient of a full-resolution quad of the stem's BatchNorm: gathered from the pooled gradient through the argmax
+// bytes as maxpool_bwd_kernel gathers it, then zeroed where bn(x) <= 0 as the ReLU's sign byte would have it.
+// n / d for 0 <= n < 2^31 by a multiplication (d >= 1 fixed per launch): the pooled gather turns every row index into (n, hi, wi),
+// and with one wavefront per SIMD -- all col_geom leaves a 64-channel map -- two hardware divisions per row are serial time
+struct FastDiv {
+    unsigned d, mul, sh;
+    __device__ __forceinline__ int div(int n) const {
+        return d == 1u ? n : (int)((unsigned)(((unsigned long long)(unsigned)n * mul) >> 32) >> sh);
+    }
+};
+inline FastDiv fast_div(int d) {
+    FastDiv f{(unsigned)d, 0u, 0u};
+    if (d > 1) {
+        int lg = 0;
+        while ((1ll << lg) < d) ++lg;           // ceil(log2 d)
+        f.mul = (unsigned)(((1ull << (31 + lg)) + (unsigned)d - 1) / (unsigned)d);
+        f.sh = (unsigned)(lg - 1);
+    }
+    return f;
+}
+
+struct PooledDy {
+    const float* __restrict__ dy;       // [N][Ho][Wo][C]
+    const unsigned* __restrict__ arg;   // one byte per element, a quad per word
+    const float* __restrict__ mean;
+    const float* __restrict__ invstd;
+    const float* __restrict__ gamma;
+    const float* __restrict__ beta;
+    int H, W, Ho, Wo, CG;
+    FastDiv byW, byH, byCG;
+    struct Raw {
+        float4 d[4];
+        unsigned a[4];      // 0xffffffff: no such window (no byte of it is a tap index)
+        int tap0;           // (kh, kw) of this quad in window 0 as kh * 3 + kw; window (jh, jw) sees it 6 jh + 2 jw lower
+        int g;
+    };
+    __device__ __forceinline__ Raw load(int row, int g, long long) const {
+        Raw w;
+        w.g = g;
+        const int t = byW.div(row), wi = row - t * W;
+        const int n = byH.div(t), hi = t - n * H;
+        w.tap0 = (hi + 1 - 2 * (hi / 2)) * 3 + (wi + 1 - 2 * (wi / 2));
+#pragma unroll
+        for (int jh = 0; jh < 2; ++jh) {            // ho = hi / 2 .. (hi + 1) / 2, wo = wi / 2 .. (wi + 1) / 2: that loop order
+            const int ho = hi / 2 + jh;
+            const bool okh = ho <= (hi + 1) / 2 && ho < Ho;
+#pragma unroll
+            for (int jw = 0; jw < 2; ++jw) {
+                const int wo = wi / 2 + jw;
+                const bool ok = okh && wo <= (wi + 1) / 2 && wo < Wo;
+                const int s = jh * 2 + jw;
+                // a window that does not exist reads window 0 again (hi / 2 < Ho, wi / 2 < Wo always) and drops it: every load
+                // unconditional, so that none of them waits behind a branch for the ones before it
+                const long long o = (((long long)n * Ho + (ok ? ho : hi / 2)) * Wo + (ok ? wo : wi / 2)) * CG + g;
+                w.d[s] = reinterpret_cast<const float4*>(dy)[o];
+                const unsigned a = arg[o];
+                w.a[s] = ok ? a : 0xffffffffu;
+            }
+        }
+        return w;
+    }
+    __device__ __forceinline__ float4 gate(const Raw& w, const float4 v) const {
+        float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float pd[4] = {w.d[k].x, w.d[k].y, w.d[k].z, w.d[k].w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (((w.a[k] >> (8 * e)) & 0xffu) == (unsigned)(w.tap0 - 6 * (k >> 1) - 2 * (k & 1))) s[e] += pd[e];
+        }
+        const float4 o = bn_affine(v, reinterpret_cast<const float4*>(mean)[w.g], reinterpret_cast<const float4*>(invstd)[w.g],
+                                   reinterpret_cast<const float4*>(gamma)[w.g], reinterpret_cast<const float4*>(beta)[w.g]);
+        if (!(o.x > 0.f)) s[0] = 0.f;
+        if (!(o.y > 0.f)) s[1] = 0.f;
+        if (!(o.z > 0.f)) s[2] = 0.f;
+        if (!(o.w > 0.f)) s[3] = 0.f;
+        return make_float4(s[0], s[1], s[2], s[3]);
+    }
+};
+__global__ __launch_bounds__(TPB) void bn_pool_bwd_partial_kernel(const PooledDy src, const BnSide a, int rows, int C, int cgb,
+                                                                  int rt, int rows_per_chunk, float* __restrict__ ws) {
+    const BnSide in[1] = {a};
+    bn_bwd_partial_body<1, 2, true>(src, in, rows, C, cgb, rt, rows_per_chunk, ws);
+}
+__global__ void bn_pool_bwd_apply_kernel(const PooledDy src, const BnSide a, const float* __restrict__ sum_dy,
+                                         const float* __restrict__ sum_dyxh, float* __restrict__ dx, long long nquads, int C,
+                                         float inv_rows, int frozen, float* __restrict__ amax) {
+    const int CG = C / 4;
+    float am = 0.f;
+    GRID_STRIDE(i, nquads) {
+        const int row = src.byCG.div((int)i), g = (int)i - row * CG;      // the entry point keeps nquads below 2^31
+        const float4 v = reinterpret_cast<const float4*>(a.x)[i];
+        const float4 d = src.gate(src.load(row, g, i), v);
+        const float4 o = bn_bwd_dx(d, a.x, i, reinterpret_cast<const float4*>(a.mean)[g], reinterpret_cast<const float4*>(a.invstd)[g],
+                                   reinterpret_cast<const float4*>(src.gamma)[g], reinterpret_cast<const float4*>(sum_dy)[g],
+                                   reinterpret_cast<const float4*>(sum_dyxh)[g], inv_rows, frozen);
+        reinterpret_cast<float4*>(dx)[i] = o;
+        am = f4absmax(am, o);
     }
     if (amax != nullptr) amax_publish(amax, am);
 }
@@ -1722,6 +2121,75 @@ extern "C" int rih_bn_bwd(const float* dy, const float* x, const float* y, const
     const long long nq = (long long)rows * (C / 4);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(nq)), dim3(TPB), 0, STREAM, dy, x, y, mean, invstd, gamma,
                        dbeta, dgamma, dx, dres, nq, C, 1.f / (float)rows, relu, frozen_stats, relu_mask, amax_dx);
+    LAUNCH_RET();
+}
+extern "C" int rih_bn_pool_fwd(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,
+                               float* y_pooled, int8_t* arg, int N, int H, int W, int C, float* amax, void* stream) {
+    if (!x || !mean || !invstd || !gamma || !beta || !y_pooled || !arg) return RIH_EINVAL;
+    if (N < 1 || H < 1 || W < 1 || C < 4 || (C % 4) != 0 || (long long)N * H * W > 0x7fffffffLL) return RIH_EINVAL;
+    if (!al16(x) || !al16(y_pooled) || !al16(arg)) return RIH_EINVAL;
+    const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
+    const long long total = (long long)N * Ho * Wo * (C / 4);
+    hipLaunchKernelGGL(bn_pool_fwd_kernel, dim3(grid_for(total)), dim3(TPB), 0, STREAM, x, mean, invstd, gamma, beta, y_pooled,
+                       reinterpret_cast<unsigned*>(arg), N, H, W, C, Ho, Wo, amax);
+    LAUNCH_RET();
+}
+extern "C" int rih_bn_pool_bwd(const float* dy_pooled, const int8_t* arg, const float* x, const float* mean, const float* invstd,
+                               const float* gamma, const float* beta, float* dx, float* dgamma, float* dbeta, int N, int H, int W,
+                               int C, int frozen_stats, float* ws, float* amax_dx, void* stream) {
+    if (!dy_pooled || !arg || !x || !mean || !invstd || !gamma || !beta || !dx || !dgamma || !dbeta || !ws) return RIH_EINVAL;
+    if (N < 1 || H < 1 || W < 1 || C < 4 || (C % 4) != 0 || (long long)N * H * W > 0x7fffffffLL) return RIH_EINVAL;
+    if (!al16(x) || !al16(dy_pooled) || !al16(arg) || !al16(dx)) return RIH_EINVAL;
+    if ((long long)N * H * W * (C / 4) > 0x7fffffffLL) return RIH_EINVAL;
+    const int rows = N * H * W;
+    const ColGeom g = col_geom(rows, C);
+    const PooledDy src{dy_pooled, reinterpret_cast<const unsigned*>(arg), mean, invstd, gamma, beta, H, W, (H + 2 - 3) / 2 + 1,
+                       (W + 2 - 3) / 2 + 1, C / 4, fast_div(W), fast_div(H), fast_div(C / 4)};
+    const BnSide a{x, mean, invstd};
+    hipLaunchKernelGGL(bn_pool_bwd_partial_kernel, dim3(g.gx, g.nchunk), dim3(TPB), 0, STREAM, src, a, rows, C, g.cgb, g.rt,
+                       g.rows_per_chunk, ws);
+    hipLaunchKernelGGL(two_sum_final_kernel, dim3((C + 3) / 4), dim3(TPB), 0, STREAM, ws, C, g.nchunk, dbeta, dgamma);
+    const long long nq = (long long)rows * (C / 4);
+    hipLaunchKernelGGL(bn_pool_bwd_apply_kernel, dim3(grid_for(nq)), dim3(TPB), 0, STREAM, src, a, dbeta, dgamma, dx, nq, C,
+                       1.f / (float)rows, frozen_stats, amax_dx);
+    LAUNCH_RET();
+}
+extern "C" int64_t rih_bn_ws2_floats(int rows, int C) {
+    if (rows < 1 || C < 4 || (C % 4) != 0) return 0;
+    const ColGeom g = col_geom(rows, C);
+    return (int64_t)3 * g.nchunk * C;
+}
+extern "C" int rih_bn_apply2(const float* xa, const float* mean_a, const float* invstd_a, const float* gamma_a,
+                             const float* beta_a, const float* xb, const float* mean_b, const float* invstd_b,
+                             const float* gamma_b, const float* beta_b, float* y, int rows, int C, int relu,
+                             uint8_t* relu_mask, float* amax, void* stream) {
+    if (!xa || !mean_a || !invstd_a || !gamma_a || !beta_a || !xb || !mean_b || !invstd_b || !gamma_b || !beta_b || !y)
+        return RIH_EINVAL;
+    if (rows < 1 || C < 4 || (C % 4) != 0) return RIH_EINVAL;
+    const long long nq = (long long)rows * (C / 4);
+    hipLaunchKernelGGL(bn_apply2_kernel, dim3(grid_for(nq)), dim3(TPB), 0, STREAM, xa, mean_a, invstd_a, gamma_a, beta_a, xb,
+                       mean_b, invstd_b, gamma_b, beta_b, y, nq, C, relu, relu_mask, amax);
+    LAUNCH_RET();
+}
+extern "C" int rih_bn_bwd2(const float* dy, const float* xa, const float* mean_a, const float* invstd_a, const float* gamma_a,
+                           const float* xb, const float* mean_b, const float* invstd_b, const float* gamma_b, float* dxa,
+                           float* dxb, float* dgamma_a, float* dbeta_a, float* dgamma_b, float* dbeta_b, int rows, int C,
+                           int relu, int frozen_a, int frozen_b, float* ws, const uint8_t* relu_mask, float* amax_dxa,
+                           float* amax_dxb, void* stream) {
+    if (!dy || !xa || !mean_a || !invstd_a || !gamma_a || !xb || !mean_b || !invstd_b || !gamma_b) return RIH_EINVAL;
+    if (!dxa || !dxb || !dgamma_a || !dbeta_a || !dgamma_b || !dbeta_b || !ws) return RIH_EINVAL;
+    if (relu && !relu_mask) return RIH_EINVAL;
+    if (rows < 1 || C < 4 || (C % 4) != 0) return RIH_EINVAL;
+    const ColGeom g = col_geom(rows, C);
+    const GatedDy src{dy, relu ? relu_mask : nullptr};
+    const BnSide a{xa, mean_a, invstd_a}, b{xb, mean_b, invstd_b};
+    hipLaunchKernelGGL(bn_bwd2_partial_kernel, dim3(g.gx, g.nchunk), dim3(TPB), 0, STREAM, src, a, b, rows, C, g.cgb, g.rt,
+                       g.rows_per_chunk, ws);
+    hipLaunchKernelGGL(three_sum_final_kernel, dim3((C + 3) / 4), dim3(TPB), 0, STREAM, ws, C, g.nchunk, dbeta_a, dbeta_b,
+                       dgamma_a, dgamma_b);
+    const long long nq = (long long)rows * (C / 4);
+    hipLaunchKernelGGL(bn_bwd2_apply_kernel, dim3(grid_for(nq)), dim3(TPB), 0, STREAM, src, a, gamma_a, b, gamma_b, dbeta_a,
+                       dgamma_a, dgamma_b, dxa, dxb, nq, C, 1.f / (float)rows, frozen_a, frozen_b, amax_dxa, amax_dxb);
     LAUNCH_RET();
 }
 

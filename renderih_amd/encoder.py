@@ -60,6 +60,39 @@ def conv_bn(cm, bn, x, residual=None, relu=False, conv_relu=False, skip=False):
     return (y, idt) if skip else y
 
 
+def _conv_stats(cm, bn, x):
+    """The convolution of a conv_bn and the `tile_stats` of its BatchNorm, without the BatchNorm."""
+    holder = ops.StatsHolder() if (ops.GEMM_STATS and bn.training) else None
+    y = ops.conv2d(x, cm.weight, cm.bias, stride=cm.stride[0], pad=cm.padding[0], stats=holder)
+    stats = ('blocks', holder.part, holder.T, holder.rows) if (holder is not None and holder.part is not None) else None
+    return y, stats
+
+
+def conv_bn_pair(cm_a, bn_a, xa, cm_b, bn_b, xb, relu=False):
+    """act(conv_bn(cm_a, bn_a, xa) + conv_bn(cm_b, bn_b, xb)) with the two BatchNorms applied in one pass, forward and backward
+    (ops.batchnorm_pair): conv_bn(.., residual=conv_bn(..)) without the inner BatchNorm's output and the gated gradient in
+    memory, same results."""
+    yb, stats_b = _conv_stats(cm_b, bn_b, xb)
+    ya, stats_a = _conv_stats(cm_a, bn_a, xa)
+    y = ops.batchnorm_pair(ya, bn_a, stats_a, yb, bn_b, stats_b, relu=relu)
+    for bn in (bn_b, bn_a):
+        if bn.training and bn.num_batches_tracked is not None:
+            _PENDING_TRACKED.append(bn.num_batches_tracked)
+    return y
+
+
+def stem_pool(cm, bn, x):
+    """maxpool3x3s2(conv_bn(cm, bn, x, relu=True)): the ResNet stem, with BatchNorm, ReLU and pool in one pass forward and
+    backward where the library has them fused (ops.batchnorm_relu_maxpool), same results."""
+    if not ops.bn_pool_fused():
+        return ops.maxpool3x3s2(conv_bn(cm, bn, x, relu=True))
+    y, stats = _conv_stats(cm, bn, x)
+    y = ops.batchnorm_relu_maxpool(y, bn, tile_stats=stats)
+    if bn.training and bn.num_batches_tracked is not None:
+        _PENDING_TRACKED.append(bn.num_batches_tracked)
+    return y
+
+
 class Bottleneck(nn.Module):
     expansion = 4
 
@@ -79,6 +112,8 @@ class Bottleneck(nn.Module):
         out, idt = conv_bn(self.conv1, self.bn1, x, relu=True, skip=True)
         out = conv_bn(self.conv2, self.bn2, out, relu=True)
         if self.downsample is not None:
+            if ops.bn_pair_fused():
+                return conv_bn_pair(self.conv3, self.bn3, out, self.downsample[0], self.downsample[1], idt, relu=True)
             idt = conv_bn(self.downsample[0], self.downsample[1], idt)
         return conv_bn(self.conv3, self.bn3, out, residual=idt, relu=True)
 
@@ -113,8 +148,7 @@ class ResNetTrunk(nn.Module):
 
     def forward(self, x):
         """x: NHWC image padded to 4 channels.  Returns x4,x3,x2,x1 (NHWC)."""
-        x = conv_bn(self.conv1, self.bn1, x, relu=True)
-        x = ops.maxpool3x3s2(x)
+        x = stem_pool(self.conv1, self.bn1, x)
         x4 = self.layer1(x)
         x3 = self.layer2(x4)
         x2 = self.layer3(x3)

@@ -1561,7 +1561,6 @@ class BatchNormFn(torch.autograd.Function):
         lib = _L()
         mean = torch.empty((Cc,), device=x.device, dtype=torch.float32)
         invstd = torch.empty((Cc,), device=x.device, dtype=torch.float32)
-        ws = torch.empty((int(lib.rih_bn_ws_floats(rows, Cc)),), device=x.device, dtype=torch.float32)
         y = torch.empty_like(x)
         if residual is not None:
             residual = _c(residual)
@@ -1570,18 +1569,7 @@ class BatchNormFn(torch.autograd.Function):
         # ybound (engine 2): the apply pass leaves max|y| there -- the operand bound of the convolution that reads y (bound_of)
 
         def run():
-            if training and tile_stats is not None and tile_stats[0] == 'blocks':   # rih_gemm's statistics epilogue
-                _, part, T, rpb = tile_stats
-                assert part.shape[2] == Cc
-                check(lib.rih_bn_stats_from_blocks(part.data_ptr(), T, Cc, rows, rpb, eps, momentum, mean.data_ptr(),
-                                                   invstd.data_ptr(), _p(rmean), _p(rvar), _stream()), 'rih_bn_stats_from_blocks')
-            elif training:
-                assert tile_stats is None
-                check(lib.rih_bn_stats(x.data_ptr(), rows, Cc, eps, momentum, mean.data_ptr(), invstd.data_ptr(),
-                                       _p(rmean), _p(rvar), ws.data_ptr(), _stream()), 'rih_bn_stats')
-            else:
-                check(lib.rih_bn_eval_stats(rmean.data_ptr(), rvar.data_ptr(), Cc, eps, mean.data_ptr(),
-                                            invstd.data_ptr(), _stream()), 'rih_bn_eval_stats')
+            _bn_statistics(lib, x, rows, Cc, training, tile_stats, eps, momentum, mean, invstd, rmean, rvar)
             check(lib.rih_bn_apply(x.data_ptr(), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
                                    _p(residual), y.data_ptr(), rows, Cc, 1 if relu else 0, _p(mask), _p(ybound), _stream()),
                   'rih_bn_apply')
@@ -1648,6 +1636,102 @@ def batchnorm(x, gamma, beta, rmean, rvar, residual=None, training=True, relu=Fa
     """input_relu: x is the output of a ReLU (Conv -> ReLU -> BN); the gradient wrt x then leaves already gated by x > 0."""
     ybound = bound_slot(x.device) if ENGINE == 2 else None
     y = BatchNormFn.apply(x, gamma, beta, rmean, rvar, residual, training, relu, eps, momentum, tile_stats, input_relu, ybound)
+    return y if ybound is None else set_bound(y, ybound)
+
+
+# y = act(BN_a(xa) + BN_b(xb)) in one apply pass and one backward (rih_bn_apply2 / rih_bn_bwd2): the end of a residual block whose
+# skip branch ends in a BatchNorm of its own.  0: BN_b's output and the gated dy go through memory, as two `batchnorm` calls.
+BN_PAIR_FUSE = os.environ.get('RIH_BN_PAIR_FUSE', '1') != '0'
+
+
+def bn_pair_fused():
+    """The fused pair is taken only from a library that has it (the numpy restatement of the ABI in the tests has not)."""
+    return BN_PAIR_FUSE and getattr(_L(), 'rih_bn_apply2', None) is not None
+
+
+def _bn_statistics(lib, x, rows, Cc, training, tile_stats, eps, momentum, mean, invstd, rmean, rvar):
+    """mean / invstd of one BatchNorm as BatchNormFn.forward obtains them (running buffers updated in training)."""
+    if training and tile_stats is not None and tile_stats[0] == 'blocks':
+        _, part, T, rpb = tile_stats
+        assert part.shape[2] == Cc
+        check(lib.rih_bn_stats_from_blocks(part.data_ptr(), T, Cc, rows, rpb, eps, momentum, mean.data_ptr(),
+                                           invstd.data_ptr(), _p(rmean), _p(rvar), _stream()), 'rih_bn_stats_from_blocks')
+    elif training:
+        assert tile_stats is None
+        ws = torch.empty((int(lib.rih_bn_ws_floats(rows, Cc)),), device=x.device, dtype=torch.float32)
+        check(lib.rih_bn_stats(x.data_ptr(), rows, Cc, eps, momentum, mean.data_ptr(), invstd.data_ptr(),
+                               _p(rmean), _p(rvar), ws.data_ptr(), _stream()), 'rih_bn_stats')
+    else:
+        check(lib.rih_bn_eval_stats(rmean.data_ptr(), rvar.data_ptr(), Cc, eps, mean.data_ptr(),
+                                    invstd.data_ptr(), _stream()), 'rih_bn_eval_stats')
+
+
+class BatchNormPairFn(torch.autograd.Function):
+    """Two nn.BatchNorm2d on NHWC rows of one shape, summed (+ ReLU).  `a` / `b`: (gamma, beta, running_mean, running_var,
+    training, eps, momentum, tile_stats) of each; statistics, running buffers and results as two BatchNormFn calls."""
+
+    @staticmethod
+    def forward(ctx, xa, xb, gamma_a, beta_a, gamma_b, beta_b, a, b, relu, ybound):
+        rmean_a, rvar_a, training_a, eps_a, mom_a, stats_a = a
+        rmean_b, rvar_b, training_b, eps_b, mom_b, stats_b = b
+        _chk(xa, xb, gamma_a, beta_a, gamma_b, beta_b, rmean_a, rvar_a, rmean_b, rvar_b)
+        xa, xb = _c(xa), _c(xb)
+        assert xa.shape == xb.shape
+        Cc = xa.shape[-1]
+        rows = xa.numel() // Cc
+        lib = _L()
+        mean_a, invstd_a, mean_b, invstd_b = (torch.empty((Cc,), device=xa.device, dtype=torch.float32) for _ in range(4))
+        y = torch.empty_like(xa)
+        mask = torch.empty((xa.numel() // 4,), device=xa.device, dtype=torch.uint8) if relu else None
+
+        def run():
+            _bn_statistics(lib, xb, rows, Cc, training_b, stats_b, eps_b, mom_b, mean_b, invstd_b, rmean_b, rvar_b)
+            _bn_statistics(lib, xa, rows, Cc, training_a, stats_a, eps_a, mom_a, mean_a, invstd_a, rmean_a, rvar_a)
+            check(lib.rih_bn_apply2(xa.data_ptr(), mean_a.data_ptr(), invstd_a.data_ptr(), gamma_a.data_ptr(), beta_a.data_ptr(),
+                                    xb.data_ptr(), mean_b.data_ptr(), invstd_b.data_ptr(), gamma_b.data_ptr(), beta_b.data_ptr(),
+                                    y.data_ptr(), rows, Cc, 1 if relu else 0, _p(mask), _p(ybound), _stream()), 'rih_bn_apply2')
+        # algorithmic bytes: a statistics pass per BatchNorm without epilogue statistics, apply reads xa, xb and writes y
+        npass = (1 if training_a and stats_a is None else 0) + (1 if training_b and stats_b is None else 0)
+        _elem_profile(xa.numel() * (4.0 * (npass + 3) + (0.25 if relu else 0.0)), 'bn_fwd', run)
+        ctx.save_for_backward(xa, xb, mask, mean_a, invstd_a, gamma_a, mean_b, invstd_b, gamma_b)
+        ctx.cfg = (training_a, training_b, relu)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xa, xb, mask, mean_a, invstd_a, gamma_a, mean_b, invstd_b, gamma_b = ctx.saved_tensors
+        training_a, training_b, relu = ctx.cfg
+        dy = _c(dy)
+        Cc = xa.shape[-1]
+        rows = xa.numel() // Cc
+        lib = _L()
+        dxa, dxb = torch.empty_like(xa), torch.empty_like(xb)
+        dga, dba, dgb, dbb = (torch.empty_like(gamma_a) for _ in range(4))
+        ws = torch.empty((int(lib.rih_bn_ws2_floats(rows, Cc)),), device=xa.device, dtype=torch.float32)
+        ba = bound_slot(xa.device) if ENGINE == 2 else None
+        bb = bound_slot(xa.device) if ENGINE == 2 else None
+        run = lambda: check(
+            lib.rih_bn_bwd2(dy.data_ptr(), xa.data_ptr(), mean_a.data_ptr(), invstd_a.data_ptr(), gamma_a.data_ptr(),
+                            xb.data_ptr(), mean_b.data_ptr(), invstd_b.data_ptr(), gamma_b.data_ptr(), dxa.data_ptr(),
+                            dxb.data_ptr(), dga.data_ptr(), dba.data_ptr(), dgb.data_ptr(), dbb.data_ptr(), rows, Cc,
+                            1 if relu else 0, 0 if training_a else 1, 0 if training_b else 1, ws.data_ptr(), _p(mask), _p(ba),
+                            _p(bb), _stream()), 'rih_bn_bwd2')
+        # algorithmic bytes: the reduction pass reads dy, xa and xb (+ 1 byte per quad of ReLU pattern), the apply pass reads them
+        # again and writes dxa and dxb
+        _elem_profile(xa.numel() * (4.0 * (2 * 3 + 2) + (0.5 if relu else 0.0)), 'bn_bwd', run)
+        if ba is not None:
+            set_bound(dxa, ba)
+            set_bound(dxb, bb)
+        return dxa, dxb, dga, dba, dgb, dbb, None, None, None, None
+
+
+def batchnorm_pair(xa, bn_a, stats_a, xb, bn_b, stats_b, relu=False):
+    """act(bn_a(xa) + bn_b(xb)) for two nn.BatchNorm2d parameter containers (their own training flags, eps and momentum);
+    stats_*: the `tile_stats` of `batchnorm`.  Call only where bn_pair_fused()."""
+    ybound = bound_slot(xa.device) if ENGINE == 2 else None
+    side = lambda bn, st: (bn.running_mean, bn.running_var, bn.training, bn.eps, bn.momentum, st)
+    y = BatchNormPairFn.apply(xa, xb, bn_a.weight, bn_a.bias, bn_b.weight, bn_b.bias, side(bn_a, stats_a), side(bn_b, stats_b),
+                              relu, ybound)
     return y if ybound is None else set_bound(y, ybound)
 
 
@@ -1724,6 +1808,75 @@ class MaxPoolFn(torch.autograd.Function):
 
 def maxpool3x3s2(x):
     return inherit_bound(MaxPoolFn.apply(x), x)         # a maximum of window values
+
+
+# maxpool3x3s2(relu(BN(x))) in one forward kernel and one backward (rih_bn_pool_fwd / rih_bn_pool_bwd): the ResNet stem.  0: the
+# BatchNorm's output and the pool's input gradient go through memory, as `batchnorm` followed by `maxpool3x3s2`.
+BN_POOL_FUSE = os.environ.get('RIH_BN_POOL_FUSE', '1') != '0'
+
+
+def bn_pool_fused():
+    """The fused stem is taken only from a library that has it (the numpy restatement of the ABI in the tests has not)."""
+    return BN_POOL_FUSE and getattr(_L(), 'rih_bn_pool_fwd', None) is not None
+
+
+class BatchNormReluMaxPoolFn(torch.autograd.Function):
+    """nn.BatchNorm2d -> ReLU -> MaxPool2d(3, 2, 1) on NHWC; statistics, running buffers and results as BatchNormFn(relu=True)
+    followed by MaxPoolFn."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, rmean, rvar, training, eps, momentum, tile_stats, ybound):
+        _chk(x, gamma, beta, rmean, rvar)
+        x = _c(x)
+        N, H, W_, Cc = x.shape
+        rows = N * H * W_
+        Ho, Wo = (H - 1) // 2 + 1, (W_ - 1) // 2 + 1
+        lib = _L()
+        mean = torch.empty((Cc,), device=x.device, dtype=torch.float32)
+        invstd = torch.empty((Cc,), device=x.device, dtype=torch.float32)
+        y = torch.empty((N, Ho, Wo, Cc), device=x.device, dtype=torch.float32)
+        arg = torch.empty((N, Ho, Wo, Cc), device=x.device, dtype=torch.int8)
+
+        def run():
+            _bn_statistics(lib, x, rows, Cc, training, tile_stats, eps, momentum, mean, invstd, rmean, rvar)
+            check(lib.rih_bn_pool_fwd(x.data_ptr(), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                      y.data_ptr(), arg.data_ptr(), N, H, W_, Cc, _p(ybound), _stream()), 'rih_bn_pool_fwd')
+        # algorithmic bytes: statistics read x once (training without epilogue statistics), the pool reads x and writes the pooled
+        # output and its argmax bytes
+        _elem_profile(x.numel() * 4.0 * ((1 if training and tile_stats is None else 0) + 1) + y.numel() * 5.0, 'bn_fwd', run)
+        ctx.save_for_backward(x, arg, mean, invstd, gamma, beta)
+        ctx.training = training
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, arg, mean, invstd, gamma, beta = ctx.saved_tensors
+        dy = _c(dy)
+        N, H, W_, Cc = x.shape
+        lib = _L()
+        dx = torch.empty_like(x)
+        dg = torch.empty_like(gamma)
+        db = torch.empty_like(gamma)
+        ws = torch.empty((int(lib.rih_bn_ws_floats(N * H * W_, Cc)),), device=x.device, dtype=torch.float32)
+        dxbound = bound_slot(x.device) if ENGINE == 2 else None
+        run = lambda: check(
+            lib.rih_bn_pool_bwd(dy.data_ptr(), arg.data_ptr(), x.data_ptr(), mean.data_ptr(), invstd.data_ptr(), gamma.data_ptr(),
+                                beta.data_ptr(), dx.data_ptr(), dg.data_ptr(), db.data_ptr(), N, H, W_, Cc,
+                                0 if ctx.training else 1, ws.data_ptr(), _p(dxbound), _stream()), 'rih_bn_pool_bwd')
+        # algorithmic bytes: the reduction pass reads x, the pooled dy and the argmax bytes, the apply pass reads them again and
+        # writes dx
+        _elem_profile(x.numel() * 4.0 * 3 + dy.numel() * 5.0 * 2, 'bn_bwd', run)
+        if dxbound is not None:
+            set_bound(dx, dxbound)
+        return dx, dg, db, None, None, None, None, None, None, None
+
+
+def batchnorm_relu_maxpool(x, bn, tile_stats=None):
+    """maxpool3x3s2(relu(bn(x))) for an nn.BatchNorm2d parameter container.  Call only where bn_pool_fused()."""
+    ybound = bound_slot(x.device) if ENGINE == 2 else None
+    y = BatchNormReluMaxPoolFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.training, bn.eps, bn.momentum,
+                                     tile_stats, ybound)
+    return y if ybound is None else set_bound(y, ybound)
 
 
 class AvgPoolFn(torch.autograd.Function):
