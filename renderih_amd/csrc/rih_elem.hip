@@ -25,6 +25,14 @@ inline int grid_for(long long n, int per_thread = 1) {
 
 #define GRID_STRIDE(i, n) \
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < (n); i += (long long)gridDim.x * blockDim.x)
+// the same loop for a body shared by several kernels: GRID_SPAN is evaluated in the __global__ function, where the compiler knows
+// that every workgroup has the launch's size and reads blockDim from the kernel arguments; in an inlined device function it goes
+// through the dispatch packet first (a dependent global load in front of every launch)
+struct GridSpan {
+    long long first, step;
+};
+#define GRID_SPAN GridSpan{(long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x}
+#define SPAN_STRIDE(i, n, sp) for (long long i = (sp).first; i < (n); i += (sp).step)
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -497,8 +505,8 @@ __global__ void bn_eval_stats_kernel(const float* __restrict__ rmean, const floa
     invstd[c] = 1.f / sqrtf(rvar[c] + eps);
 }
 
-// gamma * (x - mean) * invstd + beta of one quad: the one expression every kernel that applies a BatchNorm shares (bn_apply_kernel,
-// bn_apply2_kernel), so that the compiler contracts it into the same FMAs in each of them
+// gamma * (x - mean) * invstd + beta of one quad: the one expression every kernel that applies a BatchNorm shares, so that the
+// compiler contracts it into the same FMAs in each of them
 __device__ __forceinline__ float4 bn_affine(const float4 v, const float4 m, const float4 is, const float4 ga, const float4 be) {
     float4 o;
     o.x = (v.x - m.x) * (is.x * ga.x) + be.x;
@@ -507,24 +515,48 @@ __device__ __forceinline__ float4 bn_affine(const float4 v, const float4 m, cons
     o.w = (v.w - m.w) * (is.w * ga.w) + be.w;
     return o;
 }
+__device__ __forceinline__ float f4absmax(float am, const float4 o) {
+    return fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+}
+// zero the elements of d whose s is not positive (a NaN in s closes the gate)
+__device__ __forceinline__ void f4gate(float4& d, const float4 s) {
+    if (!(s.x > 0.f)) d.x = 0.f;
+    if (!(s.y > 0.f)) d.y = 0.f;
+    if (!(s.z > 0.f)) d.z = 0.f;
+    if (!(s.w > 0.f)) d.w = 0.f;
+}
 
-__global__ void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
-                                const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                const float* __restrict__ beta, const float* __restrict__ res, float* __restrict__ y,
-                                long long nquads, int C, int relu, unsigned char* __restrict__ mask,
-                                float* __restrict__ amax) {
+// The forward apply pass.  y = act(bn(x) + term): `term` is what is added to the BatchNorm's output before the activation -- a
+// residual quad from memory or nothing (ResidualQuad, rih_bn_apply), or a second BatchNorm (BnFwd, rih_bn_apply2).  Always
+// o = bn(x), then o += term: the fused pair equals rih_bn_apply(b) -> rih_bn_apply(a, residual) bit for bit.
+struct BnFwd {      // one BatchNorm of a forward pass: its input and its per-channel parameters
+    const float* __restrict__ x;
+    const float* __restrict__ mean;
+    const float* __restrict__ invstd;
+    const float* __restrict__ gamma;
+    const float* __restrict__ beta;
+    __device__ __forceinline__ bool on() const { return true; }
+    __device__ __forceinline__ float4 at(long long i, int g) const {
+        return bn_affine(reinterpret_cast<const float4*>(x)[i], reinterpret_cast<const float4*>(mean)[g],
+                         reinterpret_cast<const float4*>(invstd)[g], reinterpret_cast<const float4*>(gamma)[g],
+                         reinterpret_cast<const float4*>(beta)[g]);
+    }
+};
+struct ResidualQuad {
+    const float* __restrict__ res;      // nullptr: nothing is added
+    __device__ __forceinline__ bool on() const { return res != nullptr; }
+    __device__ __forceinline__ float4 at(long long i, int) const { return reinterpret_cast<const float4*>(res)[i]; }
+};
+template <class Term>
+__device__ __forceinline__ void bn_apply_body(const GridSpan sp, const BnFwd a, const Term term, float* __restrict__ y, long long nquads, int C,
+                                              int relu, unsigned char* __restrict__ mask, float* __restrict__ amax) {
     const int CG = C / 4;
     float am = 0.f;         // max |y| of this thread (-> *amax: the operand bound of the GEMM that reads y, rih_gemm engine 2)
-    GRID_STRIDE(i, nquads) {
+    SPAN_STRIDE(i, nquads, sp) {
         const int g = (int)(i % CG);
-        const float4 v = reinterpret_cast<const float4*>(x)[i];
-        const float4 m = reinterpret_cast<const float4*>(mean)[g];
-        const float4 is = reinterpret_cast<const float4*>(invstd)[g];
-        const float4 ga = reinterpret_cast<const float4*>(gamma)[g];
-        const float4 be = reinterpret_cast<const float4*>(beta)[g];
-        float4 o = bn_affine(v, m, is, ga, be);
-        if (res != nullptr) {
-            const float4 r = reinterpret_cast<const float4*>(res)[i];
+        float4 o = a.at(i, g);
+        if (term.on()) {
+            const float4 r = term.at(i, g);
             o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
         }
         if (relu) {
@@ -534,9 +566,30 @@ __global__ void bn_apply_kernel(const float* __restrict__ x, const float* __rest
             o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
         }
         reinterpret_cast<float4*>(y)[i] = o;
-        am = fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+        am = f4absmax(am, o);
     }
     if (amax != nullptr) amax_publish(amax, am);
+}
+// The kernels take their pointers one by one, not as the bodies' structs: __restrict__ tells the compiler that no store of the
+// kernel reaches an input only on a kernel parameter (on a struct member it is ignored), so only then may a load move across a store.
+__global__ void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
+                                const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                const float* __restrict__ beta, const float* __restrict__ res, float* __restrict__ y,
+                                long long nquads, int C, int relu, unsigned char* __restrict__ mask,
+                                float* __restrict__ amax) {
+    bn_apply_body(GRID_SPAN, BnFwd{x, mean, invstd, gamma, beta}, ResidualQuad{res}, y, nquads, C, relu, mask, amax);
+}
+// y = act(BN_a(xa) + BN_b(xb)): the last BatchNorm of a residual block whose skip branch ends in a BatchNorm of its own
+// (Bottleneck.downsample); see "BatchNorm pairs" below
+__global__ void bn_apply2_kernel(const float* __restrict__ xa, const float* __restrict__ mean_a,
+                                 const float* __restrict__ invstd_a, const float* __restrict__ gamma_a,
+                                 const float* __restrict__ beta_a, const float* __restrict__ xb,
+                                 const float* __restrict__ mean_b, const float* __restrict__ invstd_b,
+                                 const float* __restrict__ gamma_b, const float* __restrict__ beta_b, float* __restrict__ y,
+                                 long long nquads, int C, int relu, unsigned char* __restrict__ mask,
+                                 float* __restrict__ amax) {
+    bn_apply_body(GRID_SPAN, BnFwd{xa, mean_a, invstd_a, gamma_a, beta_a}, BnFwd{xb, mean_b, invstd_b, gamma_b, beta_b}, y, nquads, C, relu,
+                  mask, amax);
 }
 
 // Training statistics from per-row-block (mean, M2) pairs -- the statistics epilogue of rih_gemm (rih_gemm_desc.stats:
@@ -579,139 +632,31 @@ __global__ __launch_bounds__(TPB) void bn_blocks_final_kernel(const float* __res
     }
 }
 
-// BN backward pass 1: per-channel sum(dym), sum(dym * xhat), dym = dy * (y>0) when relu
-__global__ __launch_bounds__(TPB) void bn_bwd_partial_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                             const float* __restrict__ y,
-                                                             const float* __restrict__ mean,
-                                                             const float* __restrict__ invstd, int rows, int C, int cgb,
-                                                             int rt, int rows_per_chunk, int relu,
-                                                             float* __restrict__ ws,
-                                                             const unsigned char* __restrict__ mask) {
-#include "rih_bn_bwd_partial.inc"
-}
-
-// finalize: out0[C] = sum dym, out1[C] = sum dym*xhat (also the dbeta / dgamma outputs); one wavefront per channel
-__global__ __launch_bounds__(TPB) void two_sum_final_kernel(const float* __restrict__ ws, int C, int nchunk,
-                                                            float* __restrict__ out0, float* __restrict__ out1) {
-    const int lane = threadIdx.x & 63;
-    const int c = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
-    if (c >= C) return;
-    double s1 = 0.0, s2 = 0.0;
-    for (int k = lane; k < nchunk; k += 64) {
-        s1 += (double)ws[((long long)0 * nchunk + k) * C + c];
-        s2 += (double)ws[((long long)1 * nchunk + k) * C + c];
-    }
-    s1 = wave_sum_d(s1);
-    s2 = wave_sum_d(s2);
-    if (lane == 0) { out0[c] = (float)s1; out1[c] = (float)s2; }
-}
-
-__global__ void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                    const float* __restrict__ y, const float* __restrict__ mean,
-                                    const float* __restrict__ invstd, const float* __restrict__ gamma,
-                                    const float* __restrict__ sum_dy, const float* __restrict__ sum_dyxh,
-                                    float* __restrict__ dx, float* __restrict__ dres, long long nquads, int C,
-                                    float inv_rows, int relu, int frozen, const unsigned char* __restrict__ mask,
-                                    float* __restrict__ amax) {
-    const int CG = C / 4;
-    float am = 0.f;         // max |dx| of this thread (-> *amax, see bn_apply_kernel)
-    GRID_STRIDE(i, nquads) {
-        const int g = (int)(i % CG);
-        float4 d = reinterpret_cast<const float4*>(dy)[i];
-        if (relu) {
-            if (mask != nullptr) {
-                const unsigned bits = mask[i];
-                if (!(bits & 1u)) d.x = 0.f;
-                if (!(bits & 2u)) d.y = 0.f;
-                if (!(bits & 4u)) d.z = 0.f;
-                if (!(bits & 8u)) d.w = 0.f;
-            } else {
-                const float4 yy = reinterpret_cast<const float4*>(y)[i];
-                if (!(yy.x > 0.f)) d.x = 0.f;
-                if (!(yy.y > 0.f)) d.y = 0.f;
-                if (!(yy.z > 0.f)) d.z = 0.f;
-                if (!(yy.w > 0.f)) d.w = 0.f;
-            }
-        }
-        if (dres != nullptr) reinterpret_cast<float4*>(dres)[i] = d;
-        const float4 is = reinterpret_cast<const float4*>(invstd)[g];
-        const float4 ga = reinterpret_cast<const float4*>(gamma)[g];
-        // `frozen` bit 1: the input of this BatchNorm is a ReLU output (Conv -> ReLU -> BN of models/encoder.py:52-54): the
-        // gradient leaves already gated by x > 0, and the convolution's backward skips its own ReLU pass over it
-        const bool in_relu = (frozen & 2) != 0;
-        float4 o;
-        if (frozen & 1) {
-            o.x = d.x * is.x * ga.x; o.y = d.y * is.y * ga.y; o.z = d.z * is.z * ga.z; o.w = d.w * is.w * ga.w;
-            if (in_relu) {
-                const float4 v = reinterpret_cast<const float4*>(x)[i];
-                if (!(v.x > 0.f)) o.x = 0.f;
-                if (!(v.y > 0.f)) o.y = 0.f;
-                if (!(v.z > 0.f)) o.z = 0.f;
-                if (!(v.w > 0.f)) o.w = 0.f;
-            }
-        } else {
-            const float4 v = reinterpret_cast<const float4*>(x)[i];
-            const float4 m = reinterpret_cast<const float4*>(mean)[g];
-            const float4 s1 = reinterpret_cast<const float4*>(sum_dy)[g];
-            const float4 s2 = reinterpret_cast<const float4*>(sum_dyxh)[g];
-            o.x = (d.x - s1.x * inv_rows - ((v.x - m.x) * is.x) * (s2.x * inv_rows)) * (is.x * ga.x);
-            o.y = (d.y - s1.y * inv_rows - ((v.y - m.y) * is.y) * (s2.y * inv_rows)) * (is.y * ga.y);
-            o.z = (d.z - s1.z * inv_rows - ((v.z - m.z) * is.z) * (s2.z * inv_rows)) * (is.z * ga.z);
-            o.w = (d.w - s1.w * inv_rows - ((v.w - m.w) * is.w) * (s2.w * inv_rows)) * (is.w * ga.w);
-            if (in_relu) {
-                if (!(v.x > 0.f)) o.x = 0.f;
-                if (!(v.y > 0.f)) o.y = 0.f;
-                if (!(v.z > 0.f)) o.z = 0.f;
-                if (!(v.w > 0.f)) o.w = 0.f;
-            }
-        }
-        reinterpret_cast<float4*>(dx)[i] = o;
-        am = fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-    }
-    if (amax != nullptr) amax_publish(amax, am);
-}
-
-// ------------------------------------------------------------------------------------------------ BatchNorm pairs
-// y = act(BN_a(xa) + BN_b(xb)): the last BatchNorm of a residual block whose skip branch ends in a BatchNorm of its own
-// (Bottleneck.downsample).  As two rih_bn_apply calls the branch's output is written once and read once, and in the backward the
-// gated dy (`dres`) is written once and read twice, for nothing: nobody else reads either.  The kernels below form both in
+// ------------------------------------------------------------------------------------------------ BatchNorm backward
+// Three passes, each ONE body that every entry point instantiates:
+//   reduction  bn_bwd_partial_body<NX, U, AHEAD, Src>: per-channel sum(d), sum(d * xhat_k) per chunk of rows
+//   finisher   sums_final_body<NP>: the chunks' partials -> dbeta / dgamma
+//   apply      bn_bwd_apply_body<NX, Src> (bn_pool_bwd_apply_kernel for the stem): dx_k = bn_bwd_dx(d, ...)
+// d is the gradient as the BatchNorm(s) see it, and a source type Src says where it comes from: load() issues the memory requests
+// of one quad, gate() turns what came back into d.
+//   entry point      source     NX  kernels
+//   rih_bn_bwd       GatedDy    1   bn_bwd_partial_kernel<GatedDy>, two_sum_final_kernel, bn_bwd_apply_kernel<GatedDy>
+//    (relu, y only)  YGatedDy   1   bn_bwd_partial_kernel<YGatedDy>, two_sum_final_kernel, bn_bwd_apply_kernel<YGatedDy>
+//   rih_bn_bwd2      GatedDy    2   bn_bwd2_partial_kernel, three_sum_final_kernel, bn_bwd2_apply_kernel
+//   rih_bn_pool_bwd  PooledDy   1   bn_pool_bwd_partial_kernel, two_sum_final_kernel, bn_pool_bwd_apply_kernel
+// BatchNorm pairs: y = act(BN_a(xa) + BN_b(xb)), the last BatchNorm of a residual block whose skip branch ends in a BatchNorm of
+// its own (Bottleneck.downsample).  As two rih_bn_apply calls the branch's output is written once and read once, and in the
+// backward the gated dy (`dres`) is written once and read twice, for nothing: nobody else reads either.  NX = 2 forms both in
 // registers; every output is bit for bit what rih_bn_apply(b) -> rih_bn_apply(a, residual) and rih_bn_bwd(a, dres) ->
-// rih_bn_bwd(b, dy = dres) leave (tests/test_gpu_bn_fuse.py), because every sum keeps its geometry and its order (col_geom, the
-// rows of a thread in increasing order, block_col_reduce, one wavefront per channel in fp64) and every expression its shape.
-__global__ void bn_apply2_kernel(const float* __restrict__ xa, const float* __restrict__ mean_a,
-                                 const float* __restrict__ invstd_a, const float* __restrict__ gamma_a,
-                                 const float* __restrict__ beta_a, const float* __restrict__ xb,
-                                 const float* __restrict__ mean_b, const float* __restrict__ invstd_b,
-                                 const float* __restrict__ gamma_b, const float* __restrict__ beta_b, float* __restrict__ y,
-                                 long long nquads, int C, int relu, unsigned char* __restrict__ mask,
-                                 float* __restrict__ amax) {
-    const int CG = C / 4;
-    float am = 0.f;
-    GRID_STRIDE(i, nquads) {
-        const int g = (int)(i % CG);
-        const float4 va = reinterpret_cast<const float4*>(xa)[i];
-        const float4 vb = reinterpret_cast<const float4*>(xb)[i];
-        const float4 r = bn_affine(vb, reinterpret_cast<const float4*>(mean_b)[g], reinterpret_cast<const float4*>(invstd_b)[g],
-                                   reinterpret_cast<const float4*>(gamma_b)[g], reinterpret_cast<const float4*>(beta_b)[g]);
-        float4 o = bn_affine(va, reinterpret_cast<const float4*>(mean_a)[g], reinterpret_cast<const float4*>(invstd_a)[g],
-                             reinterpret_cast<const float4*>(gamma_a)[g], reinterpret_cast<const float4*>(beta_a)[g]);
-        o.x += r.x; o.y += r.y; o.z += r.z; o.w += r.w;
-        if (relu) {
-            if (mask != nullptr)
-                mask[i] = (unsigned char)((o.x > 0.f ? 1 : 0) | (o.y > 0.f ? 2 : 0) | (o.z > 0.f ? 4 : 0) | (o.w > 0.f ? 8 : 0));
-            o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-        }
-        reinterpret_cast<float4*>(y)[i] = o;
-        am = fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-    }
-    if (amax != nullptr) amax_publish(amax, am);
-}
+// rih_bn_bwd(b, dy = dres) leave (tests/test_gpu_bn_fuse.py), because both routes run the same bodies: every sum keeps its geometry
+// and its order (col_geom, the rows of a thread in increasing order, block_col_reduce, one wavefront per channel in fp64).
 
 // dy of one quad as the BatchNorm behind a ReLU sees it: from memory, zeroed where the sign byte of the forward says y <= 0
 // (mask == nullptr: no ReLU)
 struct GatedDy {
     const float* __restrict__ dy;
     const unsigned char* __restrict__ mask;
+    using By = unsigned char;
     struct Raw {
         float4 d;
         unsigned bits;
@@ -730,15 +675,33 @@ struct GatedDy {
         return w.d;
     }
 };
-struct BnSide {     // one BatchNorm of a fused backward: its input and its statistics
+// the same behind a ReLU whose forward kept no sign bytes: zeroed where the saved output y is not positive.  A type of its own,
+// not a branch in GatedDy: the second 16-byte load would sit in the registers of every kernel that gates by the byte
+struct YGatedDy {
+    const float* __restrict__ dy;
+    const float* __restrict__ y;
+    using By = float;
+    struct Raw {
+        float4 d, y;
+    };
+    __device__ __forceinline__ Raw load(int, int, long long quad) const {
+        return Raw{reinterpret_cast<const float4*>(dy)[quad], reinterpret_cast<const float4*>(y)[quad]};
+    }
+    __device__ __forceinline__ float4 gate(Raw w, const float4) const {
+        f4gate(w.d, w.y);
+        return w.d;
+    }
+};
+struct BnSide {     // one BatchNorm of a backward pass: its input and its statistics
     const float* __restrict__ x;
     const float* __restrict__ mean;
     const float* __restrict__ invstd;
 };
 
-// Backward pass 1 over NX BatchNorms that share one dy: ws[0] = sum d per chunk, ws[1 + k] = sum d * xhat_k.  The geometry and
-// the order of bn_bwd_partial_kernel (rih_bn_bwd_partial.inc), sum for sum: U rows per iteration with all their loads in
-// flight, accumulated in row order (how many rows are in flight changes no sum: every thread adds its rows one after the other).
+// Backward pass 1 over NX BatchNorms that share one d: ws[0] = sum d per chunk, ws[1 + k] = sum d * xhat_k.  U rows per iteration
+// with all their loads in flight, accumulated in row order (how many rows are in flight changes no sum: every thread adds its
+// rows one after the other).  Four rows of one BatchNorm are eight 16-byte loads (+ the mask bytes) per lane; one row per
+// iteration keeps this two-stream reduction at ~3.5 TB/s (profiles/r02/bench_kernel_stats_final.csv: 2.5 ms per step).
 template <int NX, int U, bool AHEAD, class Src>
 __device__ __forceinline__ void bn_bwd_partial_body(const Src src, const BnSide (&in)[NX], int rows, int C, int cgb, int rt,
                                                     int rows_per_chunk, float* __restrict__ ws) {
@@ -821,91 +784,134 @@ __device__ __forceinline__ void bn_bwd_partial_body(const Src src, const BnSide 
         for (int k = 0; k <= NX; ++k) *reinterpret_cast<float4*>(ws + ((long long)k * nchunk + chunk) * C + g * 4) = acc[k];
     }
 }
+template <class Src>     // GatedDy, YGatedDy
+__global__ __launch_bounds__(TPB) void bn_bwd_partial_kernel(const Src src, const BnSide a, int rows, int C, int cgb, int rt,
+                                                             int rows_per_chunk, float* __restrict__ ws) {
+    const BnSide in[1] = {a};
+    bn_bwd_partial_body<1, 4, false>(src, in, rows, C, cgb, rt, rows_per_chunk, ws);
+}
 __global__ __launch_bounds__(TPB) void bn_bwd2_partial_kernel(const GatedDy src, const BnSide a, const BnSide b, int rows, int C,
                                                               int cgb, int rt, int rows_per_chunk, float* __restrict__ ws) {
     const BnSide in[2] = {a, b};
     bn_bwd_partial_body<2, 4, false>(src, in, rows, C, cgb, rt, rows_per_chunk, ws);
 }
 
-// two_sum_final_kernel with a third plane: sum d (both dbeta: the branch's dy is the gated dy), sum d*xhat_a, sum d*xhat_b
-__global__ __launch_bounds__(TPB) void three_sum_final_kernel(const float* __restrict__ ws, int C, int nchunk,
-                                                              float* __restrict__ out0a, float* __restrict__ out0b,
-                                                              float* __restrict__ out1, float* __restrict__ out2) {
+// finisher: out[p][C] = the sum over the chunks of plane p of ws -- sum d (dbeta), sum d * xhat_k (dgamma_k); one wavefront per
+// channel, lanes stride over the chunks, fp64 xor-shuffle reduction.  out0b: a second copy of plane 0, or nullptr (a pair's two
+// dbeta are one sum: the branch's dy is the gated dy)
+template <int NP>
+__device__ __forceinline__ void sums_final_body(const float* __restrict__ ws, int C, int nchunk, float* const (&out)[NP],
+                                                float* __restrict__ out0b) {
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x * (TPB / 64) + (threadIdx.x >> 6);
     if (c >= C) return;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    double s[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) s[p] = 0.0;
     for (int k = lane; k < nchunk; k += 64) {
-        s0 += (double)ws[((long long)0 * nchunk + k) * C + c];
-        s1 += (double)ws[((long long)1 * nchunk + k) * C + c];
-        s2 += (double)ws[((long long)2 * nchunk + k) * C + c];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) s[p] += (double)ws[((long long)p * nchunk + k) * C + c];
     }
-    s0 = wave_sum_d(s0);
-    s1 = wave_sum_d(s1);
-    s2 = wave_sum_d(s2);
-    if (lane == 0) { out0a[c] = (float)s0; out0b[c] = (float)s0; out1[c] = (float)s1; out2[c] = (float)s2; }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) s[p] = wave_sum_d(s[p]);
+    if (lane != 0) return;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) out[p][c] = (float)s[p];
+    if (out0b != nullptr) out0b[c] = (float)s[0];
+}
+__global__ __launch_bounds__(TPB) void two_sum_final_kernel(const float* __restrict__ ws, int C, int nchunk,
+                                                            float* __restrict__ out0, float* __restrict__ out1) {
+    float* const out[2] = {out0, out1};
+    sums_final_body<2>(ws, C, nchunk, out, nullptr);
+}
+__global__ __launch_bounds__(TPB) void three_sum_final_kernel(const float* __restrict__ ws, int C, int nchunk,
+                                                              float* __restrict__ out0a, float* __restrict__ out0b,
+                                                              float* __restrict__ out1, float* __restrict__ out2) {
+    float* const out[3] = {out0a, out1, out2};
+    sums_final_body<3>(ws, C, nchunk, out, out0b);
 }
 
-// dx of one quad: the two formulas of bn_bwd_apply_kernel (`frozen` as there; v is read only where they need it)
-__device__ __forceinline__ float4 bn_bwd_dx(const float4 d, const float* __restrict__ x, long long i, const float4 m,
-                                            const float4 is, const float4 ga, const float4 s1, const float4 s2,
-                                            float inv_rows, int frozen) {
-    const bool in_relu = (frozen & 2) != 0;
-    float4 o;
-    if (frozen & 1) {
+// what the apply pass needs of one BatchNorm besides its BnSide; sum_dyxh is the finisher's dgamma
+struct BnGrad {
+    const float* __restrict__ gamma;
+    const float* __restrict__ sum_dyxh;
+    float* __restrict__ dx;
+    int frozen;
+    float* __restrict__ amax;
+};
+// dx of one quad from its d.  `frozen` bit 0: the statistics are the running ones, dx = d * invstd * gamma.  Bit 1: the input of
+// this BatchNorm is a ReLU output (Conv -> ReLU -> BN of models/encoder.py:52-54): the gradient leaves already gated by x > 0, and
+// the convolution's backward skips its own ReLU pass over it.  x is read only where one of the two needs it.
+__device__ __forceinline__ float4 bn_bwd_dx(const float4 d, const BnSide& in, const BnGrad& gr, const float* __restrict__ sum_dy,
+                                            long long i, int g, float inv_rows) {
+    const bool stats_frozen = (gr.frozen & 1) != 0, in_relu = (gr.frozen & 2) != 0;
+    const float4 is = reinterpret_cast<const float4*>(in.invstd)[g];
+    const float4 ga = reinterpret_cast<const float4*>(gr.gamma)[g];
+    float4 o, v;
+    if (!stats_frozen || in_relu) v = reinterpret_cast<const float4*>(in.x)[i];
+    if (stats_frozen) {
         o.x = d.x * is.x * ga.x; o.y = d.y * is.y * ga.y; o.z = d.z * is.z * ga.z; o.w = d.w * is.w * ga.w;
-        if (in_relu) {
-            const float4 v = reinterpret_cast<const float4*>(x)[i];
-            if (!(v.x > 0.f)) o.x = 0.f;
-            if (!(v.y > 0.f)) o.y = 0.f;
-            if (!(v.z > 0.f)) o.z = 0.f;
-            if (!(v.w > 0.f)) o.w = 0.f;
-        }
     } else {
-        const float4 v = reinterpret_cast<const float4*>(x)[i];
+        const float4 m = reinterpret_cast<const float4*>(in.mean)[g];
+        const float4 s1 = reinterpret_cast<const float4*>(sum_dy)[g];
+        const float4 s2 = reinterpret_cast<const float4*>(gr.sum_dyxh)[g];
         o.x = (d.x - s1.x * inv_rows - ((v.x - m.x) * is.x) * (s2.x * inv_rows)) * (is.x * ga.x);
         o.y = (d.y - s1.y * inv_rows - ((v.y - m.y) * is.y) * (s2.y * inv_rows)) * (is.y * ga.y);
         o.z = (d.z - s1.z * inv_rows - ((v.z - m.z) * is.z) * (s2.z * inv_rows)) * (is.z * ga.z);
         o.w = (d.w - s1.w * inv_rows - ((v.w - m.w) * is.w) * (s2.w * inv_rows)) * (is.w * ga.w);
-        if (in_relu) {
-            if (!(v.x > 0.f)) o.x = 0.f;
-            if (!(v.y > 0.f)) o.y = 0.f;
-            if (!(v.z > 0.f)) o.z = 0.f;
-            if (!(v.w > 0.f)) o.w = 0.f;
-        }
     }
+    if (in_relu) f4gate(o, v);
     return o;
 }
-__device__ __forceinline__ float f4absmax(float am, const float4 o) {
-    return fmaxf(fmaxf(am, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-}
 
+// Backward pass 3 over NX BatchNorms that share one d; dres != nullptr: d itself is an output too (the gradient of a residual)
+template <int NX, class Src>
+__device__ __forceinline__ void bn_bwd_apply_body(const GridSpan sp, const Src src, const BnSide (&in)[NX], const BnGrad (&gr)[NX],
+                                                  const float* __restrict__ sum_dy, float* __restrict__ dres, long long nquads,
+                                                  int C, float inv_rows) {
+    const int CG = C / 4;
+    float am[NX];           // max |dx| of this thread (-> *amax, see bn_apply_body)
+#pragma unroll
+    for (int k = 0; k < NX; ++k) am[k] = 0.f;
+    SPAN_STRIDE(i, nquads, sp) {
+        const int g = (int)(i % CG);
+        const float4 d = src.gate(src.load(0, 0, i), make_float4(0, 0, 0, 0));
+        if (dres != nullptr) reinterpret_cast<float4*>(dres)[i] = d;
+#pragma unroll
+        for (int k = 0; k < NX; ++k) {
+            const float4 o = bn_bwd_dx(d, in[k], gr[k], sum_dy, i, g, inv_rows);
+            reinterpret_cast<float4*>(gr[k].dx)[i] = o;
+            am[k] = f4absmax(am[k], o);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NX; ++k) {
+        // amax_publish's staging words are one array: the second call must not overwrite it under the first's reader
+        if (k > 0) __syncthreads();
+        if (gr[k].amax != nullptr) amax_publish(gr[k].amax, am[k]);
+    }
+}
+// pointers one by one for __restrict__, as bn_apply_kernel; `by`: the source's second pointer, sign bytes or y
+template <class Src>     // GatedDy, YGatedDy
+__global__ void bn_bwd_apply_kernel(const float* __restrict__ dy, const typename Src::By* __restrict__ by,
+                                    const float* __restrict__ x, const float* __restrict__ mean,
+                                    const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                    const float* __restrict__ sum_dy, const float* __restrict__ sum_dyxh,
+                                    float* __restrict__ dx, float* __restrict__ dres, long long nquads, int C,
+                                    float inv_rows, int frozen, float* __restrict__ amax) {
+    const BnSide in[1] = {{x, mean, invstd}};
+    const BnGrad gr[1] = {{gamma, sum_dyxh, dx, frozen, amax}};
+    bn_bwd_apply_body<1>(GRID_SPAN, Src{dy, by}, in, gr, sum_dy, dres, nquads, C, inv_rows);
+}
 __global__ void bn_bwd2_apply_kernel(const GatedDy src, const BnSide a, const float* __restrict__ gamma_a, const BnSide b,
                                      const float* __restrict__ gamma_b, const float* __restrict__ sum_dy,
                                      const float* __restrict__ sum_dyxh_a, const float* __restrict__ sum_dyxh_b,
                                      float* __restrict__ dxa, float* __restrict__ dxb, long long nquads, int C,
                                      float inv_rows, int frozen_a, int frozen_b, float* __restrict__ amax_a,
                                      float* __restrict__ amax_b) {
-    const int CG = C / 4;
-    float ama = 0.f, amb = 0.f;
-    GRID_STRIDE(i, nquads) {
-        const int g = (int)(i % CG);
-        const float4 d = src.gate(src.load(0, 0, i), make_float4(0, 0, 0, 0));
-        const float4 s1 = reinterpret_cast<const float4*>(sum_dy)[g];
-        const float4 oa = bn_bwd_dx(d, a.x, i, reinterpret_cast<const float4*>(a.mean)[g],
-                                    reinterpret_cast<const float4*>(a.invstd)[g], reinterpret_cast<const float4*>(gamma_a)[g], s1,
-                                    reinterpret_cast<const float4*>(sum_dyxh_a)[g], inv_rows, frozen_a);
-        const float4 ob = bn_bwd_dx(d, b.x, i, reinterpret_cast<const float4*>(b.mean)[g],
-                                    reinterpret_cast<const float4*>(b.invstd)[g], reinterpret_cast<const float4*>(gamma_b)[g], s1,
-                                    reinterpret_cast<const float4*>(sum_dyxh_b)[g], inv_rows, frozen_b);
-        reinterpret_cast<float4*>(dxa)[i] = oa;
-        reinterpret_cast<float4*>(dxb)[i] = ob;
-        ama = f4absmax(ama, oa);
-        amb = f4absmax(amb, ob);
-    }
-    if (amax_a != nullptr) amax_publish(amax_a, ama);
-    __syncthreads();        // amax_publish's staging words are one array: the second call must not overwrite it under the first's reader
-    if (amax_b != nullptr) amax_publish(amax_b, amb);
+    const BnSide in[2] = {a, b};
+    const BnGrad gr[2] = {{gamma_a, sum_dyxh_a, dxa, frozen_a, amax_a}, {gamma_b, sum_dyxh_b, dxb, frozen_b, amax_b}};
+    bn_bwd_apply_body<2>(GRID_SPAN, src, in, gr, sum_dy, nullptr, nquads, C, inv_rows);
 }
 
 // ------------------------------------------------------------------------------------------------ BatchNorm -> ReLU -> max-pool
@@ -913,8 +919,8 @@ __global__ void bn_bwd2_apply_kernel(const GatedDy src, const BnSide a, const fl
 // backward.  Fused, neither full-resolution tensor exists: the forward pools relu(bn(x)) over its nine taps in registers, the
 // backward gathers the gradient of a full-resolution quad from its <= 4 covering windows.  Same results as rih_bn_apply ->
 // rih_maxpool3x3s2_fwd and rih_maxpool3x3s2_bwd -> rih_bn_bwd, bit for bit (tests/test_gpu_bn_fuse.py): the pooling rules
-// (first maximum in (kh, kw) order, NaN wins, taps outside the map skipped), the gather's order (ho, then wo, s += d) and the
-// sums' geometry are those of maxpool_fwd_kernel, maxpool_bwd_kernel and bn_bwd_partial_kernel.
+// (first maximum in (kh, kw) order, NaN wins, taps outside the map skipped) and the gather's order (ho, then wo, s += d) are those
+// of maxpool_fwd_kernel and maxpool_bwd_kernel, and the sums are bn_bwd_partial_body's on col_geom's geometry, as rih_bn_bwd's.
 __global__ void bn_pool_fwd_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                    const float* __restrict__ invstd, const float* __restrict__ gamma,
                                    const float* __restrict__ beta, float* __restrict__ y, unsigned* __restrict__ arg, int N, int H,
@@ -1033,11 +1039,9 @@ struct PooledDy {
         }
         const float4 o = bn_affine(v, reinterpret_cast<const float4*>(mean)[w.g], reinterpret_cast<const float4*>(invstd)[w.g],
                                    reinterpret_cast<const float4*>(gamma)[w.g], reinterpret_cast<const float4*>(beta)[w.g]);
-        if (!(o.x > 0.f)) s[0] = 0.f;
-        if (!(o.y > 0.f)) s[1] = 0.f;
-        if (!(o.z > 0.f)) s[2] = 0.f;
-        if (!(o.w > 0.f)) s[3] = 0.f;
-        return make_float4(s[0], s[1], s[2], s[3]);
+        float4 d = make_float4(s[0], s[1], s[2], s[3]);
+        f4gate(d, o);
+        return d;
     }
 };
 __global__ __launch_bounds__(TPB) void bn_pool_bwd_partial_kernel(const PooledDy src, const BnSide a, int rows, int C, int cgb,
@@ -1045,22 +1049,21 @@ __global__ __launch_bounds__(TPB) void bn_pool_bwd_partial_kernel(const PooledDy
     const BnSide in[1] = {a};
     bn_bwd_partial_body<1, 2, true>(src, in, rows, C, cgb, rt, rows_per_chunk, ws);
 }
+// bn_bwd_apply_body for this source, which needs what the others do not: the quad's row and x for its gate
 __global__ void bn_pool_bwd_apply_kernel(const PooledDy src, const BnSide a, const float* __restrict__ sum_dy,
                                          const float* __restrict__ sum_dyxh, float* __restrict__ dx, long long nquads, int C,
                                          float inv_rows, int frozen, float* __restrict__ amax) {
+    const BnGrad gr{src.gamma, sum_dyxh, dx, frozen, amax};
     const int CG = C / 4;
     float am = 0.f;
     GRID_STRIDE(i, nquads) {
         const int row = src.byCG.div((int)i), g = (int)i - row * CG;      // the entry point keeps nquads below 2^31
         const float4 v = reinterpret_cast<const float4*>(a.x)[i];
-        const float4 d = src.gate(src.load(row, g, i), v);
-        const float4 o = bn_bwd_dx(d, a.x, i, reinterpret_cast<const float4*>(a.mean)[g], reinterpret_cast<const float4*>(a.invstd)[g],
-                                   reinterpret_cast<const float4*>(src.gamma)[g], reinterpret_cast<const float4*>(sum_dy)[g],
-                                   reinterpret_cast<const float4*>(sum_dyxh)[g], inv_rows, frozen);
-        reinterpret_cast<float4*>(dx)[i] = o;
+        const float4 o = bn_bwd_dx(src.gate(src.load(row, g, i), v), a, gr, sum_dy, i, g, inv_rows);
+        reinterpret_cast<float4*>(gr.dx)[i] = o;
         am = f4absmax(am, o);
     }
-    if (amax != nullptr) amax_publish(amax, am);
+    if (gr.amax != nullptr) amax_publish(gr.amax, am);
 }
 
 // generic column sum (bias gradients): any C, scalar path; block = 64 channels x 4 row-threads
@@ -2115,12 +2118,21 @@ extern "C" int rih_bn_bwd(const float* dy, const float* x, const float* y, const
     if (relu && !y && !relu_mask) return RIH_EINVAL;
     if (rows < 1 || C < 4 || (C % 4) != 0) return RIH_EINVAL;
     const ColGeom g = col_geom(rows, C);
-    hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(g.gx, g.nchunk), dim3(TPB), 0, STREAM, dy, x, y, mean, invstd, rows, C,
-                       g.cgb, g.rt, g.rows_per_chunk, relu, ws, relu_mask);
-    hipLaunchKernelGGL(two_sum_final_kernel, dim3((C + 3) / 4), dim3(TPB), 0, STREAM, ws, C, g.nchunk, dbeta, dgamma);
+    const BnSide a{x, mean, invstd};
     const long long nq = (long long)rows * (C / 4);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(nq)), dim3(TPB), 0, STREAM, dy, x, y, mean, invstd, gamma,
-                       dbeta, dgamma, dx, dres, nq, C, 1.f / (float)rows, relu, frozen_stats, relu_mask, amax_dx);
+    auto passes = [&](auto src, auto by) {  // the three passes from one source of the gated dy; `by`: its second pointer
+        using Src = decltype(src);
+        hipLaunchKernelGGL(bn_bwd_partial_kernel<Src>, dim3(g.gx, g.nchunk), dim3(TPB), 0, STREAM, src, a, rows, C, g.cgb, g.rt,
+                           g.rows_per_chunk, ws);
+        hipLaunchKernelGGL(two_sum_final_kernel, dim3((C + 3) / 4), dim3(TPB), 0, STREAM, ws, C, g.nchunk, dbeta, dgamma);
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<Src>, dim3(grid_for(nq)), dim3(TPB), 0, STREAM, dy, by, x, mean, invstd, gamma,
+                           dbeta, dgamma, dx, dres, nq, C, 1.f / (float)rows, frozen_stats, amax_dx);
+    };
+    const uint8_t* mask = relu ? relu_mask : nullptr;
+    if (relu && !relu_mask)
+        passes(YGatedDy{dy, y}, y);
+    else
+        passes(GatedDy{dy, mask}, mask);
     LAUNCH_RET();
 }
 extern "C" int rih_bn_pool_fwd(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta,

@@ -1619,16 +1619,7 @@ def batchnorm_update_only(x, rmean, rvar, eps=1e-5, momentum=0.1, tile_stats=Non
     with torch.no_grad():
         mean = torch.empty((Cc,), device=x.device, dtype=torch.float32)
         invstd = torch.empty((Cc,), device=x.device, dtype=torch.float32)
-        if tile_stats is not None and tile_stats[0] == 'blocks':
-            _, part, T, rpb = tile_stats
-            assert part.shape[2] == Cc
-            check(lib.rih_bn_stats_from_blocks(part.data_ptr(), T, Cc, rows, rpb, eps, momentum, mean.data_ptr(),
-                                               invstd.data_ptr(), _p(rmean), _p(rvar), _stream()), 'rih_bn_stats_from_blocks')
-        else:
-            assert tile_stats is None
-            ws = torch.empty((int(lib.rih_bn_ws_floats(rows, Cc)),), device=x.device, dtype=torch.float32)
-            check(lib.rih_bn_stats(x.data_ptr(), rows, Cc, eps, momentum, mean.data_ptr(), invstd.data_ptr(),
-                                   _p(rmean), _p(rvar), ws.data_ptr(), _stream()), 'rih_bn_stats')
+        _bn_statistics(lib, x, rows, Cc, True, tile_stats, eps, momentum, mean, invstd, rmean, rvar)
 
 
 def batchnorm(x, gamma, beta, rmean, rvar, residual=None, training=True, relu=False, eps=1e-5, momentum=0.1, tile_stats=None,

@@ -48,6 +48,18 @@ def test_pair_refuses_what_it_cannot_do(host_kernels):
     TB.test_pair_refuses_what_it_cannot_do()
 
 
+@pytest.mark.parametrize('rows,Cc', TB.MASK_Y_SHAPES[:3])
+def test_bwd_gated_by_mask_is_bitwise_gated_by_y(host_kernels, rows, Cc):
+    assert TB.check_bwd_mask_equals_y_shape(rows, Cc) == 24
+
+
+@pytest.mark.parametrize('regime', TB.MASK_Y_REGIMES)
+def test_bwd_gated_by_mask_is_bitwise_gated_by_y_multi_chunk_shape(host_kernels, regime):
+    k = TB.MASK_Y_REGIMES.index(regime)
+    frozen, with_dres = TB.mask_y_flags()[3 * k]        # (0, dres), (1, no dres), (3, dres)
+    TB.check_bwd_mask_equals_y(*TB.MASK_Y_SHAPES[3], frozen, with_dres, regime, seed=k)
+
+
 @pytest.mark.parametrize('N,H,W,Cc', TB.POOL_SHAPES[:5])
 def test_stem_is_bitwise_the_four_call_sequence(host_kernels, N, H, W, Cc):
     assert TB.check_pool_shape(N, H, W, Cc) == 12

@@ -2,13 +2,15 @@
   * the pair y = act(BN_a(xa) + BN_b(xb)) -- rih_bn_apply2 / rih_bn_bwd2 -- against rih_bn_apply(b) -> rih_bn_apply(a, residual)
     and rih_bn_bwd(a, dres) -> rih_bn_bwd(b, dy = dres);
   * the stem maxpool3x3s2(relu(BN(x))) -- rih_bn_pool_fwd / rih_bn_pool_bwd -- against rih_bn_apply(relu, mask) ->
-    rih_maxpool3x3s2_fwd and rih_maxpool3x3s2_bwd -> rih_bn_bwd.
+    rih_maxpool3x3s2_fwd and rih_maxpool3x3s2_bwd -> rih_bn_bwd;
+  * the two gates of rih_bn_bwd behind a ReLU, the forward's sign bytes and y > 0, against each other.
 
 Every comparison is BITWISE, on int32 views; no tolerances.  One thing is not a property of either source and is taken out of the
 comparison: the sign and payload bits of a NaN.  IEEE 754 leaves them open when several operands of one operation are NaN; this
 hardware takes them from the first NaN operand, and the compiler orders the factors of a contracted product, and places a negation
-among them, per kernel (in bn_bwd_apply_kernel `t - xhat * (s2 / rows)` is fma(-xhat, s2 / rows, t), in bn_bwd2_apply_kernel the
-same source line is fma(-(s2 / rows), xhat, t)).  With the bits of NaNs compared too, exactly the 'nan' regime failed, on dxa / dxb
+among them, per kernel -- per instantiation even of one source line: bn_bwd_apply_kernel and bn_bwd2_apply_kernel both take
+`t - xhat * (s2 / rows)` from bn_bwd_dx, and it has been compiled to fma(-xhat, s2 / rows, t) in the one and to
+fma(-(s2 / rows), xhat, t) in the other.  With the bits of NaNs compared too, exactly the 'nan' regime failed, on dxa / dxb
 under training statistics, at every shape (first: (1, 4, relu 0, frozen 0 0)); all other regimes, +-inf included, were equal.  So
 every NaN is mapped to one pattern before the comparison: NaNs must sit at the same places, everything else must have the same bits.
 
@@ -206,6 +208,56 @@ def test_pair_refuses_what_it_cannot_do():
     assert lib.rih_bn_apply2(P, P, P, P, P, P, P, P, P, P, P, 2, 6, 1, 0, 0, st) != 0            # C % 4
     assert lib.rih_bn_apply2(P, P, P, P, P, 0, P, P, P, P, P, 2, 8, 1, 0, 0, st) != 0            # no xb
     assert lib.rih_bn_bwd2(P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, 2, 8, 1, 0, 0, P, 0, 0, 0, st) != 0      # ReLU without its mask
+
+
+# ------------------------------------------------------------------------------------------------ the two gates of rih_bn_bwd
+MASK_Y_SHAPES = PAIR_SHAPES[:4]     # one row; a tail shorter than four rows per thread; more than one chunk; more than one quad per thread
+MASK_Y_REGIMES = ('random', 'beta_neg', 'nan')
+
+
+def check_bwd_mask_equals_y(rows, Cc, frozen, with_dres, regime, seed=0):
+    """rih_bn_bwd behind a ReLU gates dy by the forward's sign bytes or, without them, by y > 0: one rih_bn_apply(relu) leaves
+    both, and the two backward routes must leave the same bits.  `frozen`: the two bits of frozen_stats."""
+    lib, st = _lib()
+    case = (rows, Cc, frozen, with_dres, regime)
+    p = pair_problem(rows, Cc, regime, seed)
+    n = rows * Cc
+    mean, invstd = _statistics(lib, st, p, 'a', rows, Cc, frozen & 1)
+    P = lambda t: t.data_ptr()
+    y, mask = Out(n), Out(n // 4, torch.uint8)
+    assert lib.rih_bn_apply(P(p['xa']), P(mean), P(invstd), P(p['gamma_a']), P(p['beta_a']), 0, y.ptr(), rows, Cc, 1, mask.ptr(), 0,
+                            st) == 0
+    routes = []
+    for by_mask in (True, False):
+        o = {'dx': Out(n), 'dres': Out(n), 'dgamma': Out(Cc), 'dbeta': Out(Cc), 'ws': Out(int(lib.rih_bn_ws_floats(rows, Cc)))}
+        bound = _bound()
+        assert lib.rih_bn_bwd(P(p['dy']), P(p['xa']), 0 if by_mask else y.ptr(), P(mean), P(invstd), P(p['gamma_a']), o['dx'].ptr(),
+                              o['dres'].ptr() if with_dres else 0, o['dgamma'].ptr(), o['dbeta'].ptr(), rows, Cc, 1, frozen,
+                              o['ws'].ptr(), mask.ptr() if by_mask else 0, P(bound), st) == 0
+        routes.append((o, bound))
+    _sync()
+    (a, ba), (b, bb) = routes
+    for name in ('dx', 'dres', 'dgamma', 'dbeta'):      # dres not asked for: both still poison
+        _same(a[name], b[name], name, case)
+    a['ws'].bits(), b['ws'].bits()
+    assert torch.equal(ba.max().cpu(), bb.max().cpu()), 'bound of dx differs: %s' % (case,)
+
+
+def mask_y_flags():
+    return list(itertools.product((0, 1, 2, 3), (True, False)))      # frozen_stats, with dres
+
+
+def check_bwd_mask_equals_y_shape(rows, Cc):
+    k = 0
+    for (frozen, with_dres), regime in itertools.product(mask_y_flags(), MASK_Y_REGIMES):
+        check_bwd_mask_equals_y(rows, Cc, frozen, with_dres, regime, seed=k)
+        k += 1
+    return k
+
+
+@pytest.mark.parametrize('rows,Cc', MASK_Y_SHAPES)
+def test_bwd_gated_by_mask_is_bitwise_gated_by_y(rows, Cc):
+    assert check_bwd_mask_equals_y_shape(rows, Cc) == 24
 
 
 # ------------------------------------------------------------------------------------------------ the stem
