@@ -702,6 +702,24 @@ int rih_contact_search(const float* verts_main, const float* verts_sub, const in
                        int tip_class, int64_t* anchor_id, float* elastic, int64_t* mask, int64_t* vertex_contact, int B, int V,
                        int A, int D, void* stream);
 
+/* Two-hand mesh collision count, the gate behind the pose optimiser (pose_data_optimize/collision/CollisionFilter.py and
+ * CollisionCheck.py, which ask FCL for contact points; csrc/rih_collision.hip, ABI 31; renderih_amd.collision).  Counted here:
+ * INTERSECTING TRIANGLE PAIRS, a lower bound of FCL's contact points, so the reference's thresholds do not carry over.  One
+ * launch for B frames, one workgroup per (frame, 256 main faces).  verts_main[B][Vm][3], verts_sub[B][Vs][3];
+ * faces_main[Fm][3], faces_sub[Fs][3] (range-checked against Vm and Vs by the HOST); any sizes.
+ *   orient(a,b,c,d) = dot(cross(b - a, c - a), d - a).  An edge (p,q) pierces a triangle (a,b,c) when orient(a,b,c,p) and
+ *   orient(a,b,c,q) have strictly opposite signs and orient(p,q,a,b), orient(p,q,b,c), orient(p,q,c,a) are all > 0 or all < 0.
+ *   Main face i and sub face j intersect when their boxes overlap and one of the six edge-against-triangle tests pierces.
+ *   Strict throughout: coplanar, touching, zero-area and NaN configurations do not intersect; a face with a vertex that is
+ *   not finite, or with a normal cross(v1 - v0, v2 - v0) that is exactly zero, intersects nothing.
+ * pairs_main[B][Fm] = per main face the number of sub faces it intersects (plain stores); pairs_sub[B][Fs] and count[B] = the
+ * same per sub face and per frame, ADDED with integer atomics: both must be zero on entry.  Nothing is read back by the host;
+ * integer sums only, so two runs are bit-identical.
+ * RIH_EINVAL: a null pointer, B, Vm, Vs, Fm or Fs < 1, more than 2^31 - 1 workgroups. */
+int rih_collision_count(const float* verts_main, const float* verts_sub, const int32_t* faces_main, const int32_t* faces_sub,
+                        int32_t* pairs_main, int32_t* pairs_sub, int32_t* count, int B, int Vm, int Vs, int Fm, int Fs,
+                        void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Fused mesh loss   (core/Loss.py:68-164 GraphLoss.calc_loss, :201-277 calc_loss_GCN; aux loss disabled there)
  * Constant topology of one hand (device pointers, uploaded once by the caller):
@@ -760,7 +778,7 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc, opt state, adam dev entry (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 30
+#define RIH_ABI_VERSION 31
 #define RIH_ABI_NSIZES 14
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);

@@ -242,7 +242,8 @@ SIGNATURES = {
     'rih_plateau_step': (c_i, [C.c_void_p, c_f, C.c_void_p]),
     'rih_contact_search': (c_i, [c_f, c_f, C.c_void_p, c_f, C.c_void_p, C.c_void_p, c_fl, c_fl, c_fl, c_i, C.c_void_p, c_f,
                                  C.c_void_p, C.c_void_p, c_i, c_i, c_i, c_i, C.c_void_p]),
-    'rih_mesh_loss': (c_i, [C.POINTER(MeshTopo), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_fl,
+    'rih_collision_count': (c_i, [c_f, c_f] + [C.c_void_p] * 5 + [c_i] * 5 + [C.c_void_p]),
+    'rih_mesh_loss':(c_i, [C.POINTER(MeshTopo), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_fl,
                             c_f, c_f, c_f, c_f, c_f, c_i, C.c_void_p]),
     'rih_mesh_loss_final': (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, C.c_void_p]),
     'rih_mano_loss': (c_i, [C.POINTER(MeshTopo), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_f, c_fl,
@@ -268,7 +269,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 30    # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 31   # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 
