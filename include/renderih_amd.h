@@ -682,6 +682,49 @@ int rih_adam_dev(const rih_adam_dev_entry* table, int ntensors, int64_t max_n, c
                  float beta2, float eps, void* stream);
 int rih_plateau_step(rih_opt_state* state, const float* loss, void* stream);
 
+/* Fitting MANO pose and shape to 3-D joints (utils/mano_from_3djoint/: AIK.py `adaptive_IK`, utils.py `mat2aa`,
+ * convert2mano.py:158-204; csrc/rih_joint_fit.hip, ABI 32; renderih_amd.joint_fit).  fp32 in and out, no atomics, every sum in a
+ * fixed order (two runs are bit-identical), nothing read back: all of it can be captured in a hipGraph.
+ * rih_aik: `adaptive_IK(template, joints[b])` for B hands in one launch (RIH_AIK_HANDS_PER_GROUP hands per workgroup), in double
+ *   on the fp32 inputs.  tmpl[21][3] (one per call), joints[B][21][3] in the reference's joint order (wrist, then thumb, index,
+ *   middle, ring, little); normalize = 1 first scales the joints by |T9 - T0| / |P9 - P0| and moves joint 0 onto T0
+ *   (convert2mano.py:167-169).  R[B][16][3][3]: slot 0 the root rotation, the others in the reference's ID2ROT order.
+ *   Deviations from the reference: the root is always the PROPER rotation maximising tr(R H) (rih_procrustes.h; the reference
+ *   returns a reflection where det(V U^T) = -1 and no singular value is below 1e-4); a bone whose cross product with its
+ *   template bone is exactly zero gets the identity (the reference: NaN); the cosine is clamped to [-1, 1]; no twist.
+ * rih_mat2aa_fwd: aa = mat2aa(R) for N matrices R[N][3][3]: the quaternion of the selected one of mat2quat's four branches
+ *   (eps 1e-6), quat2aa, NaN components -> 0.  period > 0 (N a multiple of it, 0 <= skip < period): the first `skip` matrices
+ *   of every `period` are left out -- aa[N / period * (period - skip)][3] is compact, and head (unless NULL) receives the
+ *   left-out matrices [N / period * skip][9] (the root rotation as rih_mano_fwd takes it).  period = 0: all N.
+ * rih_mat2aa_bwd: g_R[N][9] from g_aa (compact as above): the derivative of the selected branch; at sin^2 = 0 that of aa = 2 v;
+ *   zero where the forward gave NaN or the term under the square root is not positive.  Left-out matrices receive
+ *   g_head[N / period * skip][9] (zero if NULL): with (16, 1) g_R is the whole gradient of a hand's 16 matrices.
+ * rih_joint_l1 (one workgroup): jr = j - j[:, 0], diff = jr - target, loss[b] = mean |diff[b]| over the 63 values,
+ *   total[0] = sum_b loss[b], dj[b][k] = sign(diff) / 63 for k >= 1 (sign(0) = 0), dj[b][0] = -sum_k dj[b][k].  history
+ *   (unless NULL) [hist_rows][B]: row state->step receives loss (no row outside 0..hist_rows-1 is written).
+ * rih_lr_linear_step (one thread): every group's lr = base_lr * (n_iter - step) / n_iter in double, in that order of
+ *   operations (convert2mano.py:202-203 after iteration `step`), then step += 1.  Runs after rih_adam_dev, in the place of
+ *   rih_plateau_step; the only writer of `state`.  rih_lr_linear lives in DEVICE memory, 8-byte aligned.
+ * rih_fit_select (workgroup = hand): where loss[b] < best_loss[b] (a NaN never is) best_P[b][144], best_beta[b][10] and
+ *   best_loss[b] take P, beta and loss.  Launched between rih_joint_l1 and rih_adam_dev: the parameters that gave the loss.
+ * RIH_EINVAL: a null pointer that is not optional, B or N < 1, normalize other than 0 / 1, a (period, skip) outside the above,
+ *   a history without state or rows. */
+#define RIH_AIK_HANDS_PER_GROUP 8
+#define RIH_MAT2AA_TPB 256
+typedef struct rih_lr_linear {
+    double base_lr;
+    int64_t n_iter;
+} rih_lr_linear;
+int rih_aik(const float* tmpl, const float* joints, int normalize, float* R, int B, void* stream);
+int rih_mat2aa_fwd(const float* R, float* aa, float* head, int64_t N, int period, int skip, void* stream);
+int rih_mat2aa_bwd(const float* R, const float* g_aa, const float* g_head, float* g_R, int64_t N, int period, int skip,
+                   void* stream);
+int rih_joint_l1(const float* j, const float* target, const rih_opt_state* state, float* loss, float* total, float* dj,
+                 float* history, int hist_rows, int B, void* stream);
+int rih_lr_linear_step(rih_opt_state* state, const rih_lr_linear* sched, void* stream);
+int rih_fit_select(const float* loss, const float* P, const float* beta, float* best_loss, float* best_P, float* best_beta,
+                   int B, void* stream);
+
 /* Contact search of the pose optimiser's driver (pose_data_optimize/batch_optimize_mocap_origin.py: `search_anchors` :62-130 on
  * the anchors and face normals of `update_scene` :260-270; csrc/rih_contact.hip, ABI 27; renderih_amd.contact_search).  One
  * launch for B frames, one workgroup per frame, not differentiable.  verts_main / verts_sub[B][V][3]: the two hands' vertices,
@@ -778,7 +821,7 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc, opt state, adam dev entry (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 31
+#define RIH_ABI_VERSION 32
 #define RIH_ABI_NSIZES 14
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);

@@ -99,6 +99,11 @@ class OptState(C.Structure):
                 ('patience', C.c_int32), ('ngroups', C.c_int32), ('reserved', C.c_int32)]
 
 
+class LrLinear(C.Structure):
+    """rih_lr_linear: the device block of rih_lr_linear_step."""
+    _fields_ = [('base_lr', C.c_double), ('n_iter', C.c_int64)]
+
+
 class AdamDevEntry(C.Structure):
     _fields_ = [('p', C.c_void_p), ('g', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p), ('prev', C.c_void_p),
                 ('n', C.c_int64), ('group', C.c_int32), ('period', C.c_int32), ('skip', C.c_int32), ('reserved', C.c_int32)]
@@ -240,6 +245,12 @@ SIGNATURES = {
     'rih_nature_bwd': (c_i, [c_f] * 7 + [c_i, c_i, C.c_void_p]),
     'rih_adam_dev': (c_i, [C.c_void_p, c_i, c_l, C.c_void_p, c_fl, c_fl, c_fl, C.c_void_p]),
     'rih_plateau_step': (c_i, [C.c_void_p, c_f, C.c_void_p]),
+    'rih_aik': (c_i, [c_f, c_f, c_i, c_f, c_i, C.c_void_p]),
+    'rih_mat2aa_fwd': (c_i, [c_f, c_f, c_f, c_l, c_i, c_i, C.c_void_p]),
+    'rih_mat2aa_bwd': (c_i, [c_f, c_f, c_f, c_f, c_l, c_i, c_i, C.c_void_p]),
+    'rih_joint_l1': (c_i, [c_f, c_f, C.c_void_p, c_f, c_f, c_f, c_f, c_i, c_i, C.c_void_p]),
+    'rih_lr_linear_step': (c_i, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rih_fit_select': (c_i, [c_f, c_f, c_f, c_f, c_f, c_f, c_i, C.c_void_p]),
     'rih_contact_search': (c_i, [c_f, c_f, C.c_void_p, c_f, C.c_void_p, C.c_void_p, c_fl, c_fl, c_fl, c_i, C.c_void_p, c_f,
                                  C.c_void_p, C.c_void_p, c_i, c_i, c_i, c_i, C.c_void_p]),
     'rih_collision_count': (c_i, [c_f, c_f] + [C.c_void_p] * 5 + [c_i] * 5 + [C.c_void_p]),
@@ -269,7 +280,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 31   # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 32   # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 

@@ -113,13 +113,18 @@ class DeviceAdamPlateau:
             r.n, r.group, r.period, r.skip = e['p'].numel(), int(e['group']), int(e['period']), int(e['skip'])
         self.table.copy_(_bytes_tensor(rows, 'cpu'))
 
+    def adam(self):
+        """optimizer.step() alone (rih_adam_dev): the state block is read, not written.  A scheduler kernel follows it --
+        `step` here, rih_lr_linear_step in renderih_amd.joint_fit."""
+        ops._chk(*[e['p'] for e in self.params])
+        ops.check(ops._L().rih_adam_dev(self.table.data_ptr(), len(self.params), self.max_n, self.state.data_ptr(),
+                                        self.betas[0], self.betas[1], self.eps, ops._stream()), 'rih_adam_dev')
+
     def step(self, loss):
         """optimizer.step(); scheduler.step(loss) with `loss` a device fp32 scalar: two launches, no host read."""
-        ops._chk(loss, *[e['p'] for e in self.params])
-        L, st = ops._L(), ops._stream()
-        ops.check(L.rih_adam_dev(self.table.data_ptr(), len(self.params), self.max_n, self.state.data_ptr(), self.betas[0],
-                                 self.betas[1], self.eps, st), 'rih_adam_dev')
-        ops.check(L.rih_plateau_step(self.state.data_ptr(), loss.data_ptr(), st), 'rih_plateau_step')
+        ops._chk(loss)
+        self.adam()
+        ops.check(ops._L().rih_plateau_step(self.state.data_ptr(), loss.data_ptr(), ops._stream()), 'rih_plateau_step')
 
     def read_state(self):
         """The device block as a dict (a host read: for tests and reports)."""
