@@ -821,7 +821,7 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc, opt state, adam dev entry (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 32
+#define RIH_ABI_VERSION 33
 #define RIH_ABI_NSIZES 14
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);
@@ -1044,6 +1044,19 @@ int rih_render_raster(const float* face_rec, int B, int F, int H, int W, int cam
 int rih_render_shade(const int32_t* pix_to_face, const float* bary, const float* verts, const int32_t* faces,
                      const float* vnormals, const float* colors, const float* cams, int light_kind, int B, int V, int F,
                      int H, int W, float* rgba, void* stream);
+
+/* Silhouette IoU of two meshes from ONE set of face records (csrc/rih_render.hip, next to rih_render_raster): the reference's
+ * utils/compute_maskiou.py:263-270 (two silhouette renders, a threshold, a host copy, np.count_nonzero) as a coverage-only
+ * pass (ABI 33; renderih_amd.mask_iou).  face_rec [B][F][16] is what rih_render_setup wrote for the vertices cat(first, second) and one face table whose
+ * faces 0 .. F_left-1 belong to the first mesh and the rest to the second (0 <= F_left <= F).  A pixel is covered by a mesh
+ * exactly when rih_render_raster of that mesh's faces alone gives pix_to_face >= 0.
+ *   counts [B][3] int32 = pixels covered by the first mesh, by the second, by both; zeroed here on the stream, then summed
+ *     with integer atomics: bit-identical from run to run.
+ *   iou [B] (may be NULL) = both / (first + second - both) in fp32, 0 where the union is empty.
+ *   mask [B][H][W] uint8 (may be NULL): bit 0 first mesh, bit 1 second mesh.
+ * No host read, no floating-point atomics; capturable in a graph.  Sizes as rih_render_raster. */
+int rih_mask_iou(const float* face_rec, int B, int F, int F_left, int H, int W, int cam_kind, int32_t* counts, float* iou,
+                 uint8_t* mask, void* stream);
 
 #ifdef __cplusplus
 }

@@ -123,6 +123,7 @@ SIGNATURES = {
                                 C.c_void_p]),
     'rih_render_raster': (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, C.c_void_p, c_f, c_f, C.c_void_p]),
     'rih_render_shade': (c_i, [C.c_void_p, c_f, c_f, C.c_void_p, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f, C.c_void_p]),
+    'rih_mask_iou': (c_i, [c_f, c_i, c_i, c_i, c_i, c_i, c_i, C.c_void_p, c_f, C.c_void_p, C.c_void_p]),
     'rih_prepare_images': (c_i, [C.c_void_p, c_i, c_i, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, c_f, c_f, C.c_void_p,
                                  C.c_void_p]),
     'rih_prepare_labels': (c_i, [c_f, c_f, c_i, c_i, c_i, c_f, c_f, C.c_void_p, c_fl, c_i, c_fl, c_f, c_f, c_f, C.c_void_p]),
@@ -280,7 +281,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 32   # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 33   # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 

@@ -16,6 +16,10 @@
 //                      atomic filled the list, which makes the fragments bit-identical from run to run.
 //   rih_render_shade   one thread per pixel: vertex colour, normal and world point interpolated with the fragment's
 //                      barycentrics, hard Phong (one point light) or ambient only, hard_rgb_blend onto a white background.
+// Beside them, on the same face records:
+//   rih_mask_iou       the silhouette IoU of two meshes (utils/compute_maskiou.py:263-270; renderih_amd/mask_iou.py): the raster
+//                      kernel's tiles and pixel test, two coverage flags per pixel instead of a fragment, three integer sums
+//                      per image.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/renderih_amd.h"
@@ -115,6 +119,32 @@ __global__ __launch_bounds__(STPB) void setup_kernel(const float* __restrict__ v
 // pixel centre of column c (row r) of an S x S image in pytorch3d NDC: +X left, +Y up, row 0 at the top
 __device__ __forceinline__ float ndc(int c, int S) { return 1.f - (float)(2 * c + 1) / (float)S; }
 
+// the LREC floats of a face record that a chunk keeps in LDS
+struct Face { float x0, y0, x1, y1, x2, y2, z0, z1, z2, ia; };
+
+__device__ __forceinline__ Face load_face(const float* l) {
+    return Face{l[0], l[1], l[2], l[3], l[4], l[5], l[6], l[7], l[8], l[9]};
+}
+
+// The pixel test of raster_kernel and mask_iou_kernel, in its two steps.  A pixel centre (px, py) is covered by a face when
+// inside() holds -- w0, w1, w2 >= 0, the edge functions times 1/(area + 1e-8) -- and view_depth() is not < 0.
+__device__ __forceinline__ bool inside(const Face& f, float px, float py, float& w0, float& w1, float& w2) {
+    w0 = ((px - f.x1) * (f.y2 - f.y1) - (py - f.y1) * (f.x2 - f.x1)) * f.ia;
+    w1 = ((px - f.x2) * (f.y0 - f.y2) - (py - f.y2) * (f.x0 - f.x2)) * f.ia;
+    w2 = ((px - f.x0) * (f.y1 - f.y0) - (py - f.y0) * (f.x1 - f.x0)) * f.ia;
+    return w0 >= 0.f && w1 >= 0.f && w2 >= 0.f;
+}
+
+// zbuf of a pixel that is inside(); under the perspective camera w becomes the perspective-corrected barycentrics first
+__device__ __forceinline__ float view_depth(const Face& f, int persp, float& w0, float& w1, float& w2) {
+    if (persp) {
+        const float t0 = w0 * f.z1 * f.z2, t1 = f.z0 * w1 * f.z2, t2 = f.z0 * f.z1 * w2;
+        const float d = fmaxf(t0 + t1 + t2, 1e-8f);
+        w0 = t0 / d; w1 = t1 / d; w2 = t2 / d;
+    }
+    return w0 * f.z0 + w1 * f.z1 + w2 * f.z2;
+}
+
 __global__ __launch_bounds__(RTPB) void raster_kernel(const float* __restrict__ rec, int F, int S, int tiles_x, int persp,
                                                       int32_t* __restrict__ p2f, float* __restrict__ zbuf,
                                                       float* __restrict__ bary) {
@@ -154,21 +184,13 @@ __global__ __launch_bounds__(RTPB) void raster_kernel(const float* __restrict__ 
         __syncthreads();
         const int n = (int)cnt;
         for (int j = 0; j < n; ++j) {
-            const float x0 = lrec[j][0], y0 = lrec[j][1], x1 = lrec[j][2], y1 = lrec[j][3], x2 = lrec[j][4], y2 = lrec[j][5];
-            const float z0 = lrec[j][6], z1 = lrec[j][7], z2 = lrec[j][8], ia = lrec[j][9];
+            const Face fc = load_face(lrec[j]);
             const int fj = lidx[j];
 #pragma unroll
             for (int k = 0; k < PPT; ++k) {
-                float w0 = ((px - x1) * (y2 - y1) - (py[k] - y1) * (x2 - x1)) * ia;
-                float w1 = ((px - x2) * (y0 - y2) - (py[k] - y2) * (x0 - x2)) * ia;
-                float w2 = ((px - x0) * (y1 - y0) - (py[k] - y0) * (x1 - x0)) * ia;
-                if (!(w0 >= 0.f && w1 >= 0.f && w2 >= 0.f)) continue;
-                if (persp) {
-                    const float t0 = w0 * z1 * z2, t1 = z0 * w1 * z2, t2 = z0 * z1 * w2;
-                    const float d = fmaxf(t0 + t1 + t2, 1e-8f);
-                    w0 = t0 / d; w1 = t1 / d; w2 = t2 / d;
-                }
-                const float z = w0 * z0 + w1 * z1 + w2 * z2;
+                float w0, w1, w2;
+                if (!inside(fc, px, py[k], w0, w1, w2)) continue;
+                const float z = view_depth(fc, persp, w0, w1, w2);
                 if (z < 0.f) continue;                        // behind the image plane
                 if (bf[k] < 0 || z < bz[k] || (z == bz[k] && fj < bf[k])) {
                     bz[k] = z; bf[k] = fj; bw[k][0] = w0; bw[k][1] = w1; bw[k][2] = w2;
@@ -188,6 +210,110 @@ __global__ __launch_bounds__(RTPB) void raster_kernel(const float* __restrict__ 
         zbuf[p] = hit ? bz[k] : -1.f;
         bary[3 * p] = bw[k][0]; bary[3 * p + 1] = bw[k][1]; bary[3 * p + 2] = bw[k][2];
     }
+}
+
+// how many lanes of the wavefront hold `p`; every lane of the wavefront calls it
+__device__ __forceinline__ unsigned wave_count(bool p) {
+#if defined(__HIPCC__)
+    return (unsigned)__popcll(__ballot(p));               // 64-bit ballot: one bit per lane
+#else                                                     // host build of the tests: no ballot there, a butterfly sum
+    unsigned n = p ? 1u : 0u;
+    for (int s = 32; s > 0; s >>= 1) n += __shfl_xor(n, s);
+    return n;
+#endif
+}
+
+__global__ __launch_bounds__(STPB) void mask_zero_kernel(int32_t* __restrict__ counts, int n) {
+    const int i = blockIdx.x * STPB + threadIdx.x;
+    if (i < n) counts[i] = 0;
+}
+
+// Coverage only: raster_kernel's tiles, chunks, cull and pixel test, but a pixel keeps two flags (bit 0: some face below
+// F_left covers it, bit 1: some face from F_left on does) instead of the nearest fragment.  A face's hand is decided per face:
+// the split falls anywhere in a chunk.  counts [B][3] += (pixels with bit 0, with bit 1, with both) of this tile: a ballot and a
+// popcount per wavefront, the four wavefronts summed in LDS, one integer atomicAdd per tile and quantity (skipped when zero).
+// Under the perspective camera view_depth() is left out, because there it cannot reject.  A face that reaches the test is not
+// skipped, so its three z_i are > 0 or NaN; a NaN z_i makes the screen vertex, hence w, NaN, and such a pixel is not inside().
+// With w_i >= 0 and z_i > 0 every product t_i is >= 0, d = max(sum, 1e-8) is > 0, every t_i / d is >= 0 or NaN (inf / inf),
+// and z = sum (t_i / d) z_i is >= 0 or NaN: `z < 0` is false.  The orthographic z can be negative and is tested.
+__global__ __launch_bounds__(RTPB) void mask_iou_kernel(const float* __restrict__ rec, int F, int F_left, int S, int tiles_x,
+                                                        int persp, int32_t* __restrict__ counts, uint8_t* __restrict__ mask) {
+    __shared__ float lrec[RTPB][LREC];
+    __shared__ unsigned lhand[RTPB];
+    __shared__ unsigned cnt;
+    __shared__ unsigned wsum[RTPB / 64][3];
+    const int b = blockIdx.y;
+    const int c0 = (blockIdx.x % tiles_x) * TILE, r0 = (blockIdx.x / tiles_x) * TILE;
+    const int c1 = min(c0 + TILE, S), r1 = min(r0 + TILE, S);
+    const float m = 1.f / (float)S;       // half a pixel
+    const float xhi = ndc(c0, S) + m, xlo = ndc(c1 - 1, S) - m;
+    const float yhi = ndc(r0, S) + m, ylo = ndc(r1 - 1, S) - m;
+    const int col = c0 + (int)threadIdx.x % TILE;
+    const int row0 = r0 + (int)threadIdx.x / TILE;
+    const float px = ndc(col, S);
+    float py[PPT];
+    unsigned hit[PPT];
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        py[k] = ndc(row0 + k * (RTPB / TILE), S);
+        hit[k] = 0u;
+    }
+    const float* rb = rec + (long long)b * F * REC;
+    for (int f0 = 0; f0 < F; f0 += RTPB) {
+        if (threadIdx.x == 0) cnt = 0u;
+        __syncthreads();
+        const int f = f0 + (int)threadIdx.x;
+        if (f < F) {
+            const float* r = rb + (long long)f * REC;
+            if (!(r[1] < xlo || r[0] > xhi || r[3] < ylo || r[2] > yhi)) {
+                const unsigned slot = atomicAdd(&cnt, 1u);
+#pragma unroll
+                for (int i = 0; i < LREC; ++i) lrec[slot][i] = r[4 + i];
+                lhand[slot] = f < F_left ? 1u : 2u;
+            }
+        }
+        __syncthreads();
+        const int n = (int)cnt;
+        for (int j = 0; j < n; ++j) {
+            const Face fc = load_face(lrec[j]);
+            const unsigned h = lhand[j];
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) {
+                float w0, w1, w2;
+                if (!inside(fc, px, py[k], w0, w1, w2)) continue;
+                if (!persp && view_depth(fc, 0, w0, w1, w2) < 0.f) continue;      // perspective: cannot reject, see above
+                hit[k] |= h;
+            }
+        }
+        __syncthreads();          // the list is rewritten by the next chunk
+    }
+    unsigned c[3] = {0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const int row = row0 + k * (RTPB / TILE);
+        const bool in = col < S && row < S;               // a partial tile's pixels beyond the image count for nothing
+        const bool l = in && (hit[k] & 1u), r = in && (hit[k] & 2u);
+        c[0] += wave_count(l);
+        c[1] += wave_count(r);
+        c[2] += wave_count(l && r);
+        if (mask && in) mask[((long long)b * S + row) * S + col] = (uint8_t)hit[k];
+    }
+    const int lane = (int)threadIdx.x % 64, wave = (int)threadIdx.x / 64;
+    if (lane == 0) { wsum[wave][0] = c[0]; wsum[wave][1] = c[1]; wsum[wave][2] = c[2]; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        unsigned total = 0u;
+        for (int w = 0; w < RTPB / 64; ++w) total += wsum[w][threadIdx.x];
+        if (total) atomicAdd((unsigned*)counts + (b * 3 + (int)threadIdx.x), total);
+    }
+}
+
+// inter / union in fp32 (both are exact there: at most 4096^2 = 2^24 pixels); 0 where the union is empty
+__global__ __launch_bounds__(STPB) void mask_ratio_kernel(const int32_t* __restrict__ counts, int B, float* __restrict__ iou) {
+    const int b = blockIdx.x * STPB + threadIdx.x;
+    if (b >= B) return;
+    const int inter = counts[3 * b + 2], uni = counts[3 * b] + counts[3 * b + 1] - inter;
+    iou[b] = uni > 0 ? (float)inter / (float)uni : 0.f;
 }
 
 __global__ __launch_bounds__(STPB) void shade_kernel(const int32_t* __restrict__ p2f, const float* __restrict__ bary,
@@ -281,6 +407,22 @@ extern "C" int rih_render_raster(const float* face_rec, int B, int F, int H, int
     const int tiles = (H + TILE - 1) / TILE;
     hipLaunchKernelGGL(raster_kernel, dim3((unsigned)(tiles * tiles), B), dim3(RTPB), 0, (hipStream_t)stream, face_rec, F, H,
                        tiles, cam_kind == RIH_CAM_PERSPECTIVE ? 1 : 0, pix_to_face, zbuf, bary);
+    return (int)hipGetLastError();
+}
+
+extern "C" int rih_mask_iou(const float* face_rec, int B, int F, int F_left, int H, int W, int cam_kind, int32_t* counts,
+                            float* iou, uint8_t* mask, void* stream) {
+    if (!face_rec || !counts || bad_size(B, F, H, W) || F_left < 0 || F_left > F ||
+        (cam_kind != RIH_CAM_ORTHOGRAPHIC && cam_kind != RIH_CAM_PERSPECTIVE))
+        return RIH_EINVAL;
+    const int tiles = (H + TILE - 1) / TILE;
+    hipLaunchKernelGGL(mask_zero_kernel, dim3((unsigned)((3 * B + STPB - 1) / STPB)), dim3(STPB), 0, (hipStream_t)stream,
+                       counts, 3 * B);
+    hipLaunchKernelGGL(mask_iou_kernel, dim3((unsigned)(tiles * tiles), B), dim3(RTPB), 0, (hipStream_t)stream, face_rec, F,
+                       F_left, H, tiles, cam_kind == RIH_CAM_PERSPECTIVE ? 1 : 0, counts, mask);
+    if (iou)
+        hipLaunchKernelGGL(mask_ratio_kernel, dim3((unsigned)((B + STPB - 1) / STPB)), dim3(STPB), 0, (hipStream_t)stream,
+                           counts, B, iou);
     return (int)hipGetLastError();
 }
 

@@ -5,8 +5,10 @@ root position error; the summary keys follow the reference's printed lines (mill
 Euclidean norm of the root-offset error per sample; `mrrpe_ref_script` reproduces the reference script's printed number
 (mean absolute error per coordinate, up to sqrt(3) smaller -- its `.sum(axis=1)` runs over a size-1 joint axis).  The contact deviation `cdev`
 (utils/eval_metrics.py:36-50) is one more launch per batch (`metrics.compute_cdev`, no pytorch3d).  The IoU-binned breakdown
-of the script needs its side file (`iou_0_27w.npy`) and stays with the caller: `per_sample` carries the arrays it indexes.
+of the script is `summarize_by_iou` on `per_sample`; its side file (`iou_0_27w.npy`) is what `mask_iou.scan_annotations` builds.
 """
+import warnings
+
 import numpy as np
 import torch
 
@@ -53,3 +55,38 @@ def evaluate(network, batches, jreg_left, jreg_right, device=None):
     touching = ~np.isnan(per['cdev'])
     summary['cdev'] = float(per['cdev'][touching].mean()) if touching.any() else float('nan')
     return summary, per
+
+
+def summarize_by_iou(per_sample, iou, edges=(0.33, 0.67)):
+    """The breakdown apps/eval_interhand.py:471-536 prints per level of interaction.  `per_sample` is what `evaluate`
+    returns, `iou` [N] the two hands' silhouette IoU per sample (`mask_iou.scan_annotations`, or the script's side file),
+    `edges` the script's 0.33 and 0.67 (:232-234).  -> three dicts, for iou < lo, lo <= iou < hi and iou >= hi, each with `n`,
+    `mrrpe`, `mrrpe_ref_script`, `cdev` (a nanmean), `ori joint mpjpe` and `joint mean error` as {'mean', 'std'} in mm
+    = (left + right) / 2 of the per-hand mean and population std (:489-517), and `pa joint mean error` (:531-536).  An empty
+    bin gives NaN."""
+    from .mask_iou import iou_bins
+    bins = iou_bins(iou, edges)
+    N = bins[0].shape[0]
+    for k in ('mrrpe', 'mrrpe_ref_script', 'cdev'):
+        if len(per_sample[k]) != N:
+            raise ValueError('iou has %d samples, per_sample[%r] has %d' % (N, k, len(per_sample[k])))
+    for k in ('j_err_ori', 'j_err', 'pa_mpjpe'):
+        for s in ('left', 'right'):
+            if len(per_sample[k][s]) != N:
+                raise ValueError('iou has %d samples, per_sample[%r][%r] has %d' % (N, k, s, len(per_sample[k][s])))
+
+    def both(k, sel, stat):
+        return float((stat(per_sample[k]['left'][sel]) * 1000 + stat(per_sample[k]['right'][sel]) * 1000) / 2)
+    out = []
+    with warnings.catch_warnings():                # an empty bin: numpy's mean / std of nothing is NaN, which is the answer
+        warnings.simplefilter('ignore', RuntimeWarning)
+        for sel in bins:
+            d = {'n': int(sel.sum()),
+                 'mrrpe': float(np.mean(per_sample['mrrpe'][sel])),
+                 'mrrpe_ref_script': float(np.mean(per_sample['mrrpe_ref_script'][sel])),
+                 'cdev': float(np.nanmean(per_sample['cdev'][sel]))}
+            for name, key in (('ori joint mpjpe', 'j_err_ori'), ('joint mean error', 'j_err')):
+                d[name] = {'mean': both(key, sel, np.mean), 'std': both(key, sel, np.std)}
+            d['pa joint mean error'] = both('pa_mpjpe', sel, np.mean)
+            out.append(d)
+    return out
