@@ -821,7 +821,7 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc, opt state, adam dev entry (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 33
+#define RIH_ABI_VERSION 34
 #define RIH_ABI_NSIZES 14
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);
@@ -1057,6 +1057,31 @@ int rih_render_shade(const int32_t* pix_to_face, const float* bary, const float*
  * No host read, no floating-point atomics; capturable in a graph.  Sizes as rih_render_raster. */
 int rih_mask_iou(const float* face_rec, int B, int F, int F_left, int H, int W, int cam_kind, int32_t* counts, float* iou,
                  uint8_t* mask, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Pose-data conversion, augmentation and validity around the pose optimiser (pose_data_optimize/scripts/HandPoseConverter.py,
+ * scripts/HandPoseArguer.py, Ver2Code/NatureJudge/PoseArgue.py, Ver2Code/ValidJudge/ValidJudger.py; csrc/rih_pose_convert.hip,
+ * ABI 34; renderih_amd.pose_convert).  ONE launch, one thread per (sample, joint), every form built from one kernel body:
+ *   in_fmt   0 axis-angle [N][16][3] (hands_mean is added on the finger joints)   1 Euler degrees [N][16][3], scipy's
+ *            extrinsic 'xyz': E = Rz(c) Ry(b) Rx(a)   2 quaternion [N][16][4] (w, x, y, z), any norm > 0, 16-byte aligned
+ *   mid      0 nothing (A must be 1)   1 augmentation, u = (rih_hash(seed, (((row0 + m) * 16 + j) * 2 + which)) >> 8) * 2^-24
+ *            2 augmentation, u = uniforms[m][j][which]   (which: 0 bend, 1 splay)
+ *            d = (pos - neg) * u + neg with pos = max(min(cap, hi - angle), 0), neg = min(max(-cap, lo - angle), 0) from the
+ *            sample's ORIGINAL Euler bend (c) resp. splay (b); E' = E Rz(d_bend) Ry(d_splay).  Output row m = n * A + a
+ *            reads input row n = m / A; M = N * A output rows.
+ *   out_fmt  0 Euler degrees [M][16][3] (c = 0 at gimbal lock)   1 unit quaternion [M][16][4] with w >= 0, 16-byte aligned
+ *            2 axis-angle [M][16][3], angle in [0, pi], minus hands_mean   3 validity residual in radians: out[m][hands]
+ * tables [hands][16][RIH_POSE_TAB]: per joint invM_U_n_0 (9, row-major), invU_M_n_1 (9), the zero frame invM_U_n_0^T
+ * invU_M_n_1^T (9), hands_mean (3; 0 for the root), augmentation bend lo / hi / cap and splay lo / hi / cap (cap = 0: the
+ * joint does not move), validity bend lo / hi and splay lo / hi (-inf / +inf: no limit), the side's sign (+1 right, -1 left:
+ * the left hand's y, z flip of the quaternion and diag(1, -1, -1) on its root matrix), padding.
+ * in_second: NULL, or the second hand's quaternions for out_fmt = 3 (then out is [M][2], tables hold two hands).
+ * Results depend on (row0 + m, j) only, never on the launch geometry; inputs are not written.
+ * RIH_EINVAL: a null pointer, M < 1 or > 2^27, A < 1, A != 1 without augmentation, row0 < 0, a format out of range, mid = 2
+ * without uniforms, in_second with another out_fmt than 3. */
+#define RIH_POSE_TAB 44
+int rih_pose_convert(const float* in, const float* in_second, float* out, const float* tables, const float* uniforms,
+                     uint64_t seed, int64_t row0, int64_t M, int A, int in_fmt, int mid, int out_fmt, void* stream);
 
 #ifdef __cplusplus
 }

@@ -15,8 +15,9 @@ first batch computes what the reference's per-batch search does.
 DELIBERATE DEVIATIONS: `coef_val` and `n_iter` are restored on exit (the reference leaves the last attempt's).  `obj_anchors`
 and `obj_normals` are not handed to `set_opt_val` (mode='both' ignores them, and the fused search keeps them in LDS).  Not
 reproduced, all dead under the driver's `discrete_optimize = True`: the anchor similarity with `filter_anchor_id` (:277-287,
-:503-504), `get_joint_change` (:596-623; multiplied by 0 at :509-511, so `consistent_mask` is handed over as zeros), the Euler
-conversion and file output (:575-593), and every visualisation.
+:503-504), `get_joint_change` (:596-623; multiplied by 0 at :509-511, so `consistent_mask` is handed over as zeros), the file
+output (:593), and every visualisation.  The Euler input (:385-388) and output (:579-585) around the loop are
+`pose_convert.mocap_to_optimizer` and `pose_convert.optimizer_to_mocap`.
 """
 import torch
 
