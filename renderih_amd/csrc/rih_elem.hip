@@ -1574,7 +1574,8 @@ __global__ void scatter_rows_add_kernel(const float* __restrict__ dy, const int3
     }
 }
 
-// scalar forms: any F
+// scalar forms: any F, any alignment.  PAIR: y is 8-byte aligned and the (x, Lx) pair leaves as one 8-byte store
+template <bool PAIR>
 __global__ void cheby_fwd_scalar_kernel(const float* __restrict__ x, const int32_t* __restrict__ indptr,
                                  const int32_t* __restrict__ indices, const float* __restrict__ vals,
                                  float* __restrict__ y, int B, int V, int F) {
@@ -1590,7 +1591,12 @@ __global__ void cheby_fwd_scalar_kernel(const float* __restrict__ x, const int32
         float2 o;
         o.x = xb[(long long)v * F];
         o.y = s;
-        reinterpret_cast<float2*>(y)[i] = o;
+        if constexpr (PAIR) {
+            reinterpret_cast<float2*>(y)[i] = o;
+        } else {
+            y[2 * i] = o.x;
+            y[2 * i + 1] = o.y;
+        }
     }
 }
 
@@ -2401,24 +2407,30 @@ extern "C" int rih_scatter_rows_add(const float* dy, const int32_t* inv_ptr, con
 extern "C" int rih_cheby_fwd(const float* x, const int32_t* indptr, const int32_t* indices, const float* vals, float* y,
                              int B, int V, int F, void* stream) {
     if (!x || !indptr || !indices || !vals || !y || B < 1 || V < 1 || F < 1) return RIH_EINVAL;
-    if (F % 4 == 0 && V <= CH_MAXV && B <= 65535 && al16(x) && al16(y))
+    // the LDS and gather forms read x and write y as float4: both need F % 4 == 0 and 16-byte aligned pointers
+    const bool vec = F % 4 == 0 && al16(x) && al16(y);
+    if (vec && V <= CH_MAXV && B <= 65535)
         hipLaunchKernelGGL(cheby_fwd_lds_kernel, dim3((F / 4 + CH_FS - 1) / CH_FS, B), dim3(TPB), 0, STREAM, x, indptr, indices,
                            vals, y, V, F);
-    else if (F % 4 == 0)
+    else if (vec)
         hipLaunchKernelGGL(cheby_fwd_kernel, dim3(grid_for((long long)B * V * (F / 4))), dim3(TPB), 0, STREAM, x, indptr,
                            indices, vals, y, B, V, F);
+    else if (((uintptr_t)y & 7) == 0)
+        hipLaunchKernelGGL(cheby_fwd_scalar_kernel<true>, dim3(grid_for((long long)B * V * F)), dim3(TPB), 0, STREAM, x, indptr,
+                           indices, vals, y, B, V, F);
     else
-        hipLaunchKernelGGL(cheby_fwd_scalar_kernel, dim3(grid_for((long long)B * V * F)), dim3(TPB), 0, STREAM, x, indptr,
+        hipLaunchKernelGGL(cheby_fwd_scalar_kernel<false>, dim3(grid_for((long long)B * V * F)), dim3(TPB), 0, STREAM, x, indptr,
                            indices, vals, y, B, V, F);
     LAUNCH_RET();
 }
 extern "C" int rih_cheby_bwd(const float* dy, const int32_t* t_indptr, const int32_t* t_indices, const float* t_vals,
                              float* dx, int B, int V, int F, void* stream) {
     if (!dy || !t_indptr || !t_indices || !t_vals || !dx || B < 1 || V < 1 || F < 1) return RIH_EINVAL;
-    if (F % 4 == 0 && V <= CH_MAXV && B <= 65535 && al16(dy) && al16(dx))
+    const bool vec = F % 4 == 0 && al16(dy) && al16(dx);       // as in rih_cheby_fwd
+    if (vec && V <= CH_MAXV && B <= 65535)
         hipLaunchKernelGGL(cheby_bwd_lds_kernel, dim3((F / 4 + CH_FS - 1) / CH_FS, B), dim3(TPB), 0, STREAM, dy, t_indptr,
                            t_indices, t_vals, dx, V, F);
-    else if (F % 4 == 0)
+    else if (vec)
         hipLaunchKernelGGL(cheby_bwd_kernel, dim3(grid_for((long long)B * V * (F / 4))), dim3(TPB), 0, STREAM, dy, t_indptr,
                            t_indices, t_vals, dx, B, V, F);
     else

@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.join(HERE, 'hipcpu'))
 
 import test_gpu_bounds as TB        # noqa: E402
 import test_gpu_e2_range as TR      # noqa: E402
+import test_gpu_elem_edges as TE     # noqa: E402
 import test_gpu_flash_edges as TF    # noqa: E402
 import test_gpu_loss as TL          # noqa: E402
 import test_gpu_mano as TMANO       # noqa: E402
@@ -30,7 +31,7 @@ CPU = torch.device('cpu')
 @pytest.fixture(autouse=True)
 def _host_kernels(monkeypatch):
     from host_kernels import host_kernels_abi
-    for mod in (G, TB, TR, TL, TMANO, TRT, TF):
+    for mod in (G, TB, TR, TL, TMANO, TRT, TF, TE):
         monkeypatch.setattr(mod, 'dev', lambda: CPU)
     with host_kernels_abi():
         yield
@@ -364,6 +365,46 @@ def test_flash_edges_on_cpu():
     TF.check_dropout((1, 129, 33, 64, 4))
     TF.check_entry_points(33, 0.25)
     TF.check_refusals()
+
+
+# --------------------------------------------------------------------- tests/test_gpu_elem_edges.py on the host build of rih_elem.hip
+# Every check of the GPU file, every case: what can show here is indexing, tails, dispatch and the arithmetic's order; expf,
+# FMA contraction and the wave shuffles are the GPU's own and only its run sees them.  Left out: check_cheby_forms_bit_identical
+# (B = 65536: its 131072 LDS-form workgroups of 256 fibers take 37 s here); it runs on the GPU only.
+def test_elem_edges_layernorm_on_cpu():
+    EC = TE.EC
+    for case in EC.LN_CASES + EC.LN_MEASURED_CASES:
+        TE.check_layernorm_abi(case)
+    for case in EC.LN_SWITCH_CASES + EC.LN_PAIR_CASES:
+        TE.test_layernorm_switches_vs_fp64(case)
+    for case in EC.LN_MISALIGNED_CASES:
+        TE.check_layernorm_abi(case, off=1)
+
+
+def test_elem_edges_softmax_on_cpu():
+    EC = TE.EC
+    for case in EC.SM_CASES:
+        TE.check_softmax(case)
+    for case in EC.SM_DROPOUT_CASES:
+        TE.check_softmax_dropout(case)
+    TE.check_softmax_mask_twin()
+
+
+def test_elem_edges_cheby_gather_and_pooling_on_cpu():
+    EC = TE.EC
+    for case in EC.CH_CASES:
+        TE.check_cheby(case)
+    TE.check_cheby(EC.CH_MISALIGNED_CASE, off=1)
+    for case in EC.GS_CASES:
+        TE.check_gather(case)
+    for case in EC.MP_CASES:
+        TE.check_maxpool(case)
+    for case in EC.AP_CASES:
+        TE.check_avgpool(case)
+
+
+def test_elem_edges_refusals_on_the_host_library():
+    TE.check_refusals()
 
 
 def test_graph_and_resampling_kernels():
