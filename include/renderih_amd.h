@@ -821,7 +821,7 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc, opt state, adam dev entry (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 34
+#define RIH_ABI_VERSION 35
 #define RIH_ABI_NSIZES 14
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);
@@ -1082,6 +1082,57 @@ int rih_mask_iou(const float* face_rec, int B, int F, int F_left, int H, int W, 
 #define RIH_POSE_TAB 44
 int rih_pose_convert(const float* in, const float* in_second, float* out, const float* tables, const float* uniforms,
                      uint64_t seed, int64_t row0, int64_t M, int A, int in_fmt, int mid, int out_fmt, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The auxiliary heads of the encoders: heat-map labels, the aux loss and the heat-map decoder (dataset/heatmap.py:11-39,
+ * core/Loss.py:180-198, dataset/inference.py:113-127; csrc/rih_aux.hip, ABI 35; renderih_amd.aux_heads).  Every tensor is fp32,
+ * contiguous NCHW.  No atomics (two runs give the same bits), no host read, every call capturable in a graph; inputs are not
+ * written.  16-byte loads and stores where the plane size is a multiple of 4 and every pointer is 16-byte aligned, dwords
+ * otherwise.
+ *
+ * rih_heatmaps: joints [maps][C] (C = 2: x, y; C = 3: x, y, v) -> hms [maps][R][R],
+ *   hms[m][y][x] = exp(-((x - jx)^2 + (y - jy)^2) / (2 sigma^2)); the whole map is 0 when C = 3 and v <= 0, or when jx < 0,
+ *   jy < 0, jx >= R or jy >= R (a joint exactly at 0 is drawn, one exactly at R is not).  sigma is the generator's
+ *   sigma * scale.  RIH_EINVAL: a null pointer, maps < 1 or > 2^31, C not 2 or 3, R < 1 or > 4096, sigma <= 0.
+ *
+ * rih_aux_loss: calc_aux_loss and the gradient of its total in ONE pass: every operand read once, every gradient written once.
+ *   predictions p_hms [B][Jh][S][S], p_mask [B][2][S][S], p_dense [B][6][S][S]; labels t_mask [B][2][S][S], t_dense
+ *   [B][3][S][S], and for the heat maps EITHER t_hms [B][Jh][S][S] OR t_joints [B][Jh][C] with sigma (exactly one non-null):
+ *   the target pixel is then produced in the kernel by the device function rih_heatmaps uses and no target tensor is read.
+ *   With sl1 = SmoothL1(beta), mean over all elements, and mse = mean squared error:
+ *     mask  = sl1(p_mask - t_mask)
+ *     dense = 1/2 [ sl1(p_dense[:, 0:3] m0 - t_dense m0) + sl1(p_dense[:, 3:6] m1 - t_dense m1) ],  m0 = t_mask[:, 0:1],
+ *             m1 = t_mask[:, 1:2] as FLOAT factors: the gradient is sl1'(d) m / count for any m
+ *     hms   = mse(p_hms - t_hms)
+ *     total = weights[0] mask + weights[1] dense + weights[2] hms
+ *   weights [3] is a DEVICE array read at run time (a captured graph follows a change).  A term whose prediction pointer is NULL
+ *   is absent: its value is 0 and its gradient is not written (its label and gradient pointers are ignored).
+ *   Writes g_hms, g_mask, g_dense (d total / d prediction, shaped as the predictions) and partial [nblk][4] raw sums per
+ *   workgroup, nblk = rih_aux_loss_blocks(B, Jh, S, p_hms != NULL, p_mask != NULL || p_dense != NULL) <= 2048 (0 for sizes
+ *   the kernel refuses).
+ * rih_aux_loss_final: ONE workgroup adds the partial sums in a fixed order: out [4] = total, mask, dense, hms.
+ *   RIH_EINVAL: weights, partial or out NULL, every prediction NULL, B < 1 or > 2^20, S < 1 or > 4096, Jh < 1 or > 4096 with p_hms,
+ *   beta <= 0, both or neither of t_hms / t_joints with p_hms, t_joints with C not 2 or 3 or sigma <= 0, a present term
+ *   without its label or gradient pointer.
+ *
+ * rih_hms_decode: get_final_preds2.  hm [maps][H][W] -> preds [maps][2] (x, y), maxvals [maps]; one workgroup per map, the map
+ *   in LDS (H * W * 4 <= 65536 bytes).  (1) arg-max of the raw map, the first flat index on ties, x = idx % W, y = idx / W;
+ *   preds = (0, 0) when the maximum is <= 0.  (2) kernel > 1: zero-padded separable blur with OpenCV's fixed taps for
+ *   sigma = 0 -- 3: (1, 2, 1)/4, 5: (1, 4, 6, 4, 1)/16, 7: (1, 3.5, 7, 9, 7, 3.5, 1)/32 -- then times raw_max / blurred_max.
+ *   (3) log(max(., 1e-10)).  (4) only when 1 < x < W - 2 and 1 < y < H - 2: the five finite differences of
+ *   inference.py:57-61 and offset = -Hessian^-1 gradient when dxx dyy - dxy^2 != 0 (the two products rounded separately).
+ *   A map whose maximum is not positive gives preds = (0, 0) and maxvals = the maximum, never a NaN.  A map with a positive
+ *   maximum whose BLURRED maximum is <= 0 (kernel > 1: an isolated positive pixel among large negatives) is rescaled by
+ *   raw_max / blurred_max as the reference does, and its coordinates can then be inf or NaN, as the reference's.
+ *   RIH_EINVAL: a null pointer, maps < 1 or > 2^31, H or W < 1, H * W > 16384, kernel not 1, 3, 5 or 7. */
+int rih_heatmaps(const float* joints, float* hms, int64_t maps, int C, int R, float sigma, void* stream);
+int rih_aux_loss_blocks(int B, int Jh, int S, int has_hms, int has_mask_or_dense);
+int rih_aux_loss(const float* p_hms, const float* p_mask, const float* p_dense, const float* t_hms, const float* t_joints,
+                 const float* t_mask, const float* t_dense, const float* weights, int B, int Jh, int S, int C, float sigma,
+                 float beta, float* g_hms, float* g_mask, float* g_dense, float* partial, void* stream);
+int rih_aux_loss_final(const float* partial, const float* weights, int B, int Jh, int S, int has_hms, int has_mask_or_dense,
+                       float* out, void* stream);
+int rih_hms_decode(const float* hm, float* preds, float* maxvals, int64_t maps, int H, int W, int kernel, void* stream);
 
 #ifdef __cplusplus
 }

@@ -256,6 +256,11 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p, c_i, c_i, c_i, c_i, C.c_void_p]),
     'rih_collision_count': (c_i, [c_f, c_f] + [C.c_void_p] * 5 + [c_i] * 5 + [C.c_void_p]),
     'rih_pose_convert': (c_i, [c_f, c_f, c_f, c_f, c_f, c_u64, c_l, c_l, c_i, c_i, c_i, c_i, C.c_void_p]),
+    'rih_heatmaps': (c_i, [c_f, c_f, c_l, c_i, c_i, c_fl, C.c_void_p]),
+    'rih_aux_loss_blocks': (c_i, [c_i] * 5),
+    'rih_aux_loss': (c_i, [c_f] * 8 + [c_i, c_i, c_i, c_i, c_fl, c_fl, c_f, c_f, c_f, c_f, C.c_void_p]),
+    'rih_aux_loss_final': (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, C.c_void_p]),
+    'rih_hms_decode': (c_i, [c_f, c_f, c_f, c_l, c_i, c_i, c_i, C.c_void_p]),
     'rih_mesh_loss':(c_i, [C.POINTER(MeshTopo), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_fl,
                             c_f, c_f, c_f, c_f, c_f, c_i, C.c_void_p]),
     'rih_mesh_loss_final': (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, C.c_void_p]),
@@ -282,7 +287,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 34  # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 35  # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 

@@ -4,7 +4,8 @@ SURVEY.md 8a row a15 / 8f-2: the loss sits right after the hot path; its FLOPs a
 as PyTorch elementwise ops (fusing it into HIP kernels is the "next" row).  Semantics follow
 core/Loss.py:20-164 (GraphLoss) and :201-277 (calc_loss_GCN): SmoothL1 on 3-D vertices and regressed joints,
 MSE on normalised 2-D vertices, face-normal and edge-length terms, the same at the coarse (252-vertex) level, aux
-(hms/mask/dense) loss disabled, edge term gated by epoch >= NORM_EPOCH, right hand shifted by root_rel.
+(hms/mask/dense) loss disabled unless `aux=` hands in a renderih_amd.aux_heads loss, edge term gated by epoch >= NORM_EPOCH,
+right hand shifted by root_rel.
 
 MANO-head loss (core/Loss_mano.py: ManoLoss :62-219, mano_loss_GCN :245-335; the loss of `load_new_model`), reproduced with
 its quirks by `ManoLoss` / `mano_loss_GCN` (torch mirror) and `FusedManoLoss` / `mano_loss_GCN_fused` (csrc/rih_mano_loss.hip):
@@ -94,8 +95,11 @@ class GraphLoss:
 
 
 def calc_loss_GCN(weights, epoch, loss_left, loss_right, converter_left, converter_right, result, paramsDict,
-                  handDictList, otherInfo, v2d_l, v2d_r, v3d_l, v3d_r, root_rel, img_size=256, upsample_weight=None):
-    """core/Loss.py:201-277 (aux loss disabled there, :211)."""
+                  handDictList, otherInfo, v2d_l, v2d_r, v3d_l, v3d_r, root_rel, img_size=256, upsample_weight=None,
+                  aux=None, mask=None, dense=None, hms=None, joints2d=None, sigma=None):
+    """core/Loss.py:201-277 (aux loss disabled there, :211).  aux: an aux_heads.AuxLoss / FusedAuxLoss switches that line on --
+    calc_aux_loss on otherInfo's 'mask', 'dense', 'hms' against the labels mask, dense and hms (or joints2d with sigma) -- and
+    the call then returns (total, mano, aux_lost_dict) with the aux total inside the total."""
     w = dict(DEFAULT_WEIGHTS)
     w.update(weights or {})
     v3d_r = v3d_r + root_rel.unsqueeze(1)
@@ -115,7 +119,16 @@ def calc_loss_GCN(weights, epoch, loss_left, loss_right, converter_left, convert
     if upsample_weight is not None and loss_left.upsample_weight is not None:
         total = total + w['UPSAMPLE'] * F.smooth_l1_loss(upsample_weight - loss_left.upsample_weight,
                                                          torch.zeros_like(upsample_weight))
+    if aux is not None:
+        return _with_aux(total, mano, aux, otherInfo, mask, dense, hms, joints2d, sigma)
     return total, mano
+
+
+def _with_aux(total, mano, aux, otherInfo, mask, dense, hms, joints2d, sigma):
+    """The un-commented core/Loss.py:211: aux_lost_dict = calc_aux_loss(cfg, graph_loss_left, otherInfo, mask, dense, hms)."""
+    heads = {k: otherInfo[k] for k in ('mask', 'dense', 'hms') if k in otherInfo}
+    aux_total, aux_lost_dict = aux(heads, mask, dense, hms=hms, joints2d=joints2d, sigma=sigma)
+    return total + aux_total, mano, aux_lost_dict
 
 
 # ------------------------------------------------------------------------------------------------ MANO-head loss (mirror)
@@ -380,8 +393,10 @@ class FusedMeshLoss:
 
 
 def calc_loss_GCN_fused(fused, epoch, result, paramsDict, handDictList, otherInfo, v2d_l, v2d_r, v3d_l, v3d_r, root_rel,
-                        upsample_weight=None, upsample_target=None):
-    """`calc_loss_GCN` on the fused kernel: same total; the mano dict carries the reference's five terms.
+                        upsample_weight=None, upsample_target=None, aux=None, mask=None, dense=None, hms=None, joints2d=None,
+                        sigma=None):
+    """`calc_loss_GCN` on the fused kernel: same total; the mano dict carries the reference's five terms.  aux (an
+    aux_heads.FusedAuxLoss or AuxLoss) with the labels mask, dense and hms / joints2d: as in calc_loss_GCN, three values return.
     `upsample_weight` / `upsample_target`: the trainable up-sampling matrix and its initial value -- the UPSAMPLE term of
     core/Loss.py:222-224, which the reference adds when the up-sampling layer is not frozen (a tiny torch expression on
     one 778x252 matrix; with the default frozen layer both are None and the term is absent, as in the reference)."""
@@ -393,6 +408,8 @@ def calc_loss_GCN_fused(fused, epoch, result, paramsDict, handDictList, otherInf
                                                                 torch.zeros_like(upsample_weight))
     mano = {'vert2d_loss': terms[1], 'vert3d_loss': terms[2], 'joint_loss': terms[3], 'norm_loss': terms[4],
             'edge_loss': terms[5]}
+    if aux is not None:
+        return _with_aux(total, mano, aux, otherInfo, mask, dense, hms, joints2d, sigma)
     return total, mano
 
 
