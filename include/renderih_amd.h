@@ -821,7 +821,7 @@ int rih_mano_loss_final(const float* partial_left, const float* partial_right, c
  * this order: gemm desc, mano model, mesh topo, hconv desc, reduce desc, pack desc, ln final desc, adam entry, absmax desc,
  * conv3 desc, h2 desc, panel desc, opt state, adam dev entry (RIH_ABI_NSIZES values), so a host binding can refuse a stale binary instead of handing it
  * mis-laid-out structs. */
-#define RIH_ABI_VERSION 35
+#define RIH_ABI_VERSION 36
 #define RIH_ABI_NSIZES 14
 int rih_version(void);
 int rih_abi_sizes(int32_t* out10);
@@ -1133,6 +1133,48 @@ int rih_aux_loss(const float* p_hms, const float* p_mask, const float* p_dense, 
 int rih_aux_loss_final(const float* partial, const float* weights, int B, int Jh, int S, int has_hms, int has_mask_or_dense,
                        float* out, void* stream);
 int rih_hms_decode(const float* hm, float* preds, float* maxvals, int64_t maps, int H, int W, int kernel, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The image-to-overlay path of the demo (core/test_utils.py:46-128 `InterRender`, apps/demo.py:103-128; csrc/rih_demo.hip,
+ * ABI 36; renderih_amd.demo).  uint8 BGR in, uint8 BGR out; one launch per call, no atomics, no host read, capturable.
+ *
+ * A ragged image batch is one packed uint8 buffer `src` of `src_bytes` bytes and a DEVICE table desc [B][RIH_DEMO_DESC] of
+ * int64 rows: byte offset, H, W, pad_top, pad_left, PH, PW, reserved, ytab, xtab.  The padded image is
+ * P[r][c] = I[r - pad_top][c - pad_left] inside the H x W x 3 image and 0 outside; PH x PW is its size.  A row whose image does
+ * not lie inside [0, src_bytes), or whose H or W is outside 1 .. 32767, reads as black: no row can make the kernel read out of
+ * bounds.  The 8-bit resize of P to Sy x Sx:
+ *   PH == Sy and PW == Sx: copy.   PH == 2 Sy and PW == 2 Sx: (P[2y][2x] + P[2y][2x+1] + P[2y+1][2x] + P[2y+1][2x+1] + 2) >> 2.
+ *   otherwise the taps come from `tabs`, a 16-byte aligned DEVICE array of tab_entries x 4 int32 (s, s', a0, a1): entries
+ *   ytab .. ytab + Sy - 1 for the rows and xtab .. xtab + Sx - 1 for the columns (a range outside the array: black),
+ *   T_r = P[r][s] a0 + P[r][s'] a1,  out = clamp((((b0 (T_s >> 4)) >> 16) + ((b1 (T_s' >> 4)) >> 16) + 2) >> 2, 0, 255)
+ *   with (s, s', b0, b1) of the row entry.  The tables are built on the host (renderih_amd.demo.axis_table): integer work only
+ *   on the device.  This restates cv::resize (CV_8U, INTER_LINEAR); conformity with an OpenCV build is unverified.
+ *
+ * rih_demo_resize: out [B][Sy][Sx][3] uint8.
+ * rih_demo_prepare: `process_img` (pad2squre, resize, BGR -> RGB, / 255, (x - mean) / std in fp32 as rih_prepare_images) to
+ *   S x S; each output may be NULL (not all): norm [B][3][S][S] fp32, norm_h8 [B][S][S][8] fp16 (16-byte aligned, lanes 3..7
+ *   zero), out_u8 [B][S][S][3] the resized BGR image.
+ * rih_demo_compose: out [B][R][R][3] uint8 = trunc(fl(fl(rgb 255) mask) + fl(back fl(1 - mask))), every operation rounded to
+ *   fp32, saturated to 0 .. 255 (NaN -> 0; numpy wraps instead).  rgb: pixel i channel c at rgb[i rgb_ld + c], mask at
+ *   mask[i mask_ld], i = (b R + y) R + x.  back = the image of row b of bg_desc resized to R x R, or 255 when bg is NULL.
+ *   Channels are not swapped.
+ * rih_demo_other_view: out [B][2V][3] = cat(v_left - c, v_right - c) Rot, c = (mean(v_left) + mean(v_right)) / 2 per sample;
+ *   rot_host: 9 floats (row-major) in HOST memory, read before the launch.  Fixed summation order.
+ * rih_demo_smooth: rows_host [E][6] int64 in HOST memory, E <= RIH_DEMO_SMOOTH_MAX: p, out, last, last_v, acc (device fp32
+ *   pointers, n elements each; out may be p) and n.  stage = frames seen before: >= 3: out = 0.7 p + 0.3 (last + last_v + 0.5 acc),
+ *   else out = p; then (stage >= 1) v = out - last, (stage >= 2) acc = v - last_v, last_v = v; last = out.
+ * RIH_EINVAL: a null pointer, a size out of range (B 1 .. 65536, S / R 1 .. 32767), misaligned tabs or norm_h8. */
+#define RIH_DEMO_DESC 10
+#define RIH_DEMO_SMOOTH_MAX 16
+int rih_demo_resize(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int32_t* tabs, int64_t tab_entries, int B,
+                    int Sy, int Sx, uint8_t* out, void* stream);
+int rih_demo_prepare(const uint8_t* src, int64_t src_bytes, const int64_t* desc, const int32_t* tabs, int64_t tab_entries, int B,
+                     int S, float* norm, void* norm_h8, uint8_t* out_u8, void* stream);
+int rih_demo_compose(const float* rgb, int64_t rgb_ld, const float* mask, int64_t mask_ld, const uint8_t* bg, int64_t bg_bytes,
+                     const int64_t* bg_desc, const int32_t* tabs, int64_t tab_entries, int B, int R, uint8_t* out, void* stream);
+int rih_demo_other_view(const float* v_left, const float* v_right, const float* rot_host, int B, int V, float* out,
+                        void* stream);
+int rih_demo_smooth(const int64_t* rows_host, int E, int stage, void* stream);
 
 #ifdef __cplusplus
 }

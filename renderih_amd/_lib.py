@@ -261,6 +261,12 @@ SIGNATURES = {
     'rih_aux_loss': (c_i, [c_f] * 8 + [c_i, c_i, c_i, c_i, c_fl, c_fl, c_f, c_f, c_f, c_f, C.c_void_p]),
     'rih_aux_loss_final': (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, C.c_void_p]),
     'rih_hms_decode': (c_i, [c_f, c_f, c_f, c_l, c_i, c_i, c_i, C.c_void_p]),
+    'rih_demo_resize': (c_i, [C.c_void_p, c_l, C.c_void_p, C.c_void_p, c_l, c_i, c_i, c_i, C.c_void_p, C.c_void_p]),
+    'rih_demo_prepare': (c_i, [C.c_void_p, c_l, C.c_void_p, C.c_void_p, c_l, c_i, c_i, c_f, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'rih_demo_compose': (c_i, [c_f, c_l, c_f, c_l, C.c_void_p, c_l, C.c_void_p, C.c_void_p, c_l, c_i, c_i, C.c_void_p,
+                               C.c_void_p]),
+    'rih_demo_other_view': (c_i, [c_f, c_f, C.POINTER(C.c_float), c_i, c_i, c_f, C.c_void_p]),
+    'rih_demo_smooth': (c_i, [C.POINTER(C.c_int64), c_i, c_i, C.c_void_p]),
     'rih_mesh_loss':(c_i, [C.POINTER(MeshTopo), c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_fl,
                             c_f, c_f, c_f, c_f, c_f, c_i, C.c_void_p]),
     'rih_mesh_loss_final': (c_i, [c_f, c_f, c_i, c_f, c_f, c_f, C.c_void_p]),
@@ -287,7 +293,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 35  # = RIH_ABI_VERSION of include/renderih_amd.h
+ABI_VERSION = 36  # = RIH_ABI_VERSION of include/renderih_amd.h
 
 _lib = None
 
