@@ -19,7 +19,7 @@ SOURCES = ['rih_gemm.hip', 'rih_conv3.hip', 'rih_elem.hip', 'rih_mano.hip', 'rih
            'rih_render.hip', 'rih_mano_loss.hip', 'rih_sdf_loss.hip', 'rih_anchor.hip', 'rih_pose_prior.hip', 'rih_pose_opt.hip',
            'rih_contact.hip', 'rih_nature.hip', 'rih_collision.hip', 'rih_joint_fit.hip', 'rih_pose_convert.hip',
            'rih_aux.hip', 'rih_demo.hip']
-HEADERS = ['rih_procrustes.h', 'rih_pose_math.h', 'rih_hash.h', 'rih_e2.h']
+HEADERS = ['rih_procrustes.h', 'rih_pose_math.h', 'rih_hash.h', 'rih_e2.h', 'rih_reduce.h', 'rih_mesh_terms.h']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result',
          # hipcc's SLP pass packs neighbouring f32 adds into v_pk_add_f32, which issues at a fraction of the scalar
          # rate next to MFMAs (MI355X_MICROARCH.md, cycle constants): keep the split arithmetic scalar

@@ -16,27 +16,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/renderih_amd.h"
+#include "rih_reduce.h"
 
 namespace {
 
 constexpr int TPB = 256;
 constexpr int CHUNK = TPB * 4;                 // pixels per work item
 constexpr int MAX_BLOCKS = 2048;               // 8 workgroups per CU: every SIMD holds 8 waves of independent 16-byte loads
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum over the 256 threads of the block, in a fixed order; valid in every thread
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // nn.SmoothL1Loss(beta): 0.5 x^2 / beta below beta, |x| - 0.5 beta from beta on
 __device__ __forceinline__ float sl1(float x, float beta) {

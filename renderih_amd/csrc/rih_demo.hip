@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/renderih_amd.h"
+#include "rih_reduce.h"
 
 namespace {
 
@@ -162,12 +163,6 @@ __global__ __launch_bounds__(TPB) void demo_compose_kernel(const float* __restri
 }
 
 struct Rot { float r[9]; };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __global__ __launch_bounds__(TPB) void demo_other_view_kernel(const float* __restrict__ vl, const float* __restrict__ vr,
                                                               const Rot rot, int V, float* __restrict__ out) {

@@ -10,6 +10,7 @@
 #include <math.h>
 #include "../../include/renderih_amd.h"
 #include "rih_hash.h"
+#include "rih_reduce.h"
 
 namespace {
 
@@ -33,22 +34,6 @@ struct GridSpan {
 };
 #define GRID_SPAN GridSpan{(long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x}
 #define SPAN_STRIDE(i, n, sp) for (long long i = (sp).first; i < (n); i += (sp).step)
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // counter-based RNG for dropout: 32 uniform bits from (seed, element index) -- rih_hash.h
 __device__ __forceinline__ uint32_t drop_thresh(float p) {

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/renderih_amd.h"
+#include "rih_reduce.h"
 
 namespace {
 
@@ -1002,9 +1003,9 @@ __global__ __launch_bounds__(256) void mano_fused_kernel(Model m, const float* _
 }
 
 // ------------------------------------------------------------------------------------------------ backward
+// not rih_reduce.h's block_sum: the four wave sums are added left to right here, and the backward's bits rest on that order
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();

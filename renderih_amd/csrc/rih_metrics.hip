@@ -13,22 +13,12 @@
 #include <stdint.h>
 #include "../../include/renderih_amd.h"
 #include "rih_procrustes.h"
+#include "rih_reduce.h"
 
 namespace {
 
 constexpr int TPB = 256;
 constexpr int MAXV = 1024, MAXJ = 32;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 struct Shared {
     float pv[MAXV * 3], gv[MAXV * 3];

@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/renderih_amd.h"
+#include "rih_reduce.h"
 
 #ifndef RIH_NATURE_R
 #define RIH_NATURE_R 4
@@ -80,12 +81,6 @@ inline long long pack_floats(int H) { return 8LL * H * H + 97LL * H + 4; }
 // [2B][4][H] activations, [2B][4] (p0, p1, bce, mask), [2B] scale
 inline long long ws_floats(int B, int H) { return 2LL * B * (4LL * H + 4 + 1) + 2; }
 inline bool bad_h(int H) { return H < 64 || H > HMAX || H % 64 != 0; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __device__ __forceinline__ float leaky(float v) { return v > 0.f ? v : v * SLOPE; }
 __device__ __forceinline__ float slope_of(float act) { return act > 0.f ? 1.f : SLOPE; }

@@ -8,16 +8,11 @@
 #include <stdint.h>
 #include "../../include/renderih_amd.h"
 #include "rih_pose_math.h"
+#include "rih_reduce.h"
 
 namespace {
 
 constexpr int TPB = 256;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 inline int blocks_for(long long n) {
     long long b = (n + TPB - 1) / TPB;

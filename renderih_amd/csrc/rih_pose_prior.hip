@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/renderih_amd.h"
+#include "rih_reduce.h"
 
 namespace {
 
@@ -32,21 +33,6 @@ __constant__ float BEND_LO[15] = {-25, -4, -8, -25, -7, -8, -22, -8, -8, -25, -1
 __constant__ float BEND_HI[15] = {70, 110, 90, 80, 100, 90, 70, 90, 90, 70, 100, 90, 40, 50, 100};
 __constant__ float SPLAY_LO[15] = {-25, 1, 1, -15, 1, 1, -20, 1, 1, -25, 1, 1, -30, 1, 1};
 __constant__ float SPLAY_HI[15] = {15, 0, 0, 15, 0, 0, 30, 0, 0, 15, 0, 0, 30, 0, 0};
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum over the 256 threads of the block; the result is valid in every thread
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // max(relu(a - hi), relu(lo - a)) / 180 * pi, squared and weighted: adds to the loss, returns d loss / d a * (180 / pi)
 __device__ __forceinline__ float hinge(float a, float lo, float hi, float wgt, float& loss) {

@@ -254,6 +254,84 @@ def mano_loss_GCN(cfg, epoch, loss_left, loss_right, converter_left, converter_r
 
 
 # ------------------------------------------------------------------------------------------------ fused HIP loss
+class _FusedLoss:
+    """What FusedMeshLoss and FusedManoLoss share: the constant topology of both hands (faces, vertex->face adjacency,
+    21-joint regressor) on the host and, once per device, on the device; and the term weights that the kernels read at
+    run time.  A subclass gives `weights(B)` -> (weights[NW], counts[7]) and, for a coarse level, `_coarse()`."""
+    NW = None           # number of weights in front of the seven counts in the device slot
+
+    def __init__(self, w, loss_left, loss_right, img_size):
+        self.w = w
+        self.img_size = img_size
+        self.epoch = 0
+        self._host = {}
+        for side, gl in (('left', loss_left), ('right', loss_right)):
+            faces = gl.faces.detach().cpu().numpy().astype(np.int32)
+            V = gl.J_regressor.shape[1]
+            order = np.argsort(faces.reshape(-1), kind='stable')            # entries (face*3 + corner) grouped by vertex
+            counts = np.bincount(faces.reshape(-1), minlength=V)
+            vptr = np.zeros(V + 1, np.int32)
+            vptr[1:] = np.cumsum(counts)
+            self._host[side] = dict(faces=faces, vptr=vptr, vlist=order.astype(np.int32),
+                                    J=gl.J_regressor.detach().cpu().float().contiguous(), V=V, F=faces.shape[0],
+                                    NJ=gl.J_regressor.shape[0])
+        self._dev = {}
+
+    def device_weights(self, B, device):
+        """(weights[NW], counts[7]) as views of one device tensor that the kernels read at run time.  The tensor is
+        rewritten IN PLACE (outside any stream capture) only when the values change -- batch size, or the epoch gate of
+        the edge term (core/Loss.py:211-220, NORM_EPOCH) -- so a hipGraph captured at epoch 0 picks the edge term up
+        when the trainer calls `set_epoch()` (or this loss eagerly) at a later epoch."""
+        w, cnt = self.weights(B)
+        vals = tuple(w) + tuple(cnt)
+        # one slot per (device, batch size): evaluating this loss on another batch size between two replays of a captured
+        # step must not rewrite the weights / counts that the graph reads
+        key = ('wdev', device, B)
+        if key not in self._dev:
+            self._dev[key] = [torch.zeros(self.NW + 7, device=device, dtype=torch.float32), None]
+        slot = self._dev[key]
+        if slot[1] != vals:
+            if torch.cuda.is_available() and device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('%s: the term weights changed during stream capture (epoch gate or batch '
+                                   'size); call set_epoch() / run one eager step before capturing' % type(self).__name__)
+            slot[0].copy_(torch.tensor(vals, dtype=torch.float32))
+            slot[1] = vals
+        return slot[0][:self.NW], slot[0][self.NW:]
+
+    def set_epoch(self, epoch, B=None, device=None):
+        """Move the epoch gate (edge term on from NORM_EPOCH).  With a replayed hipGraph pass the captured batch size and
+        device so that the device-resident weights are refreshed in place (without them: every slot that exists)."""
+        self.epoch = epoch
+        if B is not None and device is not None:
+            self.device_weights(B, torch.device(device))
+        else:                                       # all captured batch sizes / devices
+            for key in [k for k in self._dev if k[0] == 'wdev']:
+                self.device_weights(key[2], key[1])
+
+    def _coarse(self, h, device):
+        """(perm on the device, Vc, pool) of the coarse level; none here."""
+        return None, 0, 0
+
+    def topo(self, side, device):
+        from ._lib import MeshTopo
+        key = (side, device)
+        if key not in self._dev:
+            h = self._host[side]
+            t = {k: torch.as_tensor(h[k], device=device) for k in ('faces', 'vptr', 'vlist')}
+            t['J'] = h['J'].to(device)
+            t['perm'], Vc, pool = self._coarse(h, device)
+            self._dev[key] = (t, MeshTopo(t['faces'].data_ptr(), t['vptr'].data_ptr(), t['vlist'].data_ptr(),
+                                          t['J'].data_ptr(), None if t['perm'] is None else t['perm'].data_ptr(),
+                                          h['V'], h['F'], h['NJ'], Vc, pool))
+        return self._dev[key][1]
+
+
+def _scaled(ctx, g_total):
+    """The backward of both fused losses: the kernels already produced the gradients, scale them by the incoming one.  Out
+    of place: the saved gradients may be read again (retain_graph); ONE multi-tensor launch instead of a clone per tensor."""
+    return tuple(torch._foreach_mul(list(ctx.saved_tensors), g_total))
+
+
 class _MeshLossFn(torch.autograd.Function):
     """Total loss of calc_loss_GCN for both hands in three launches (rih_mesh_loss x 2 + rih_mesh_loss_final); the
     kernel already produced the gradients, backward only scales them by the incoming gradient."""
@@ -288,33 +366,21 @@ class _MeshLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_total, _g_terms):
-        # out of place: the saved gradients may be read again (retain_graph); ONE multi-tensor launch instead of a clone per tensor
-        grads = torch._foreach_mul(list(ctx.saved_tensors), g_total)
-        return (None,) + tuple(grads) + (None,) * 5
+        return (None,) + _scaled(ctx, g_total) + (None,) * 5
 
 
-class FusedMeshLoss:
+class FusedMeshLoss(_FusedLoss):
     """GPU drop-in for `calc_loss_GCN` (same arguments and total) on the fused HIP kernel.  Holds the constant
     topology of both hands on the device: faces, vertex->face adjacency, 21-joint regressor, graph permutation."""
 
+    NW = 7
+
     def __init__(self, loss_left, loss_right, converter_left, converter_right, weights=None, img_size=256):
-        self.w = dict(DEFAULT_WEIGHTS)
-        self.w.update(weights or {})
-        self.img_size = img_size
-        self.epoch = 0
-        self._host = {}
-        for side, gl, conv in (('left', loss_left, converter_left), ('right', loss_right, converter_right)):
-            faces = gl.faces.detach().cpu().numpy().astype(np.int32)
-            V = gl.J_regressor.shape[1]
-            order = np.argsort(faces.reshape(-1), kind='stable')            # entries (face*3 + corner) grouped by vertex
-            counts = np.bincount(faces.reshape(-1), minlength=V)
-            vptr = np.zeros(V + 1, np.int32)
-            vptr[1:] = np.cumsum(counts)
-            perm = np.asarray(conv.graph_perm, dtype=np.int32)
-            self._host[side] = dict(faces=faces, vptr=vptr, vlist=order.astype(np.int32),
-                                    J=gl.J_regressor.detach().cpu().float().contiguous(), perm=perm, V=V, F=faces.shape[0],
-                                    NJ=gl.J_regressor.shape[0])
-        self._dev = {}
+        w = dict(DEFAULT_WEIGHTS)
+        w.update(weights or {})
+        super().__init__(w, loss_left, loss_right, img_size)
+        for side, conv in (('left', converter_left), ('right', converter_right)):
+            self._host[side]['perm'] = np.asarray(conv.graph_perm, dtype=np.int32)
         self.Vc = None
 
     def weights(self, B):
@@ -326,51 +392,18 @@ class FusedMeshLoss:
               self.w['LABEL_3D'], self.w['LABEL_2D']]
         return [0.5 * a / c for a, c in zip(lw, cnt)], [float(c) for c in cnt]
 
-    def device_weights(self, B, device):
-        """(weights[7], counts[7]) as views of one device tensor that the kernels read at run time.  The tensor is
-        rewritten IN PLACE (outside any stream capture) only when the values change -- batch size, or the epoch gate of
-        the edge term (core/Loss.py:211-220, NORM_EPOCH) -- so a hipGraph captured at epoch 0 picks the edge term up
-        when the trainer calls `set_epoch()` (or this loss eagerly) at a later epoch."""
-        w, cnt = self.weights(B)
-        vals = tuple(w) + tuple(cnt)
-        # one slot per (device, batch size): evaluating this loss on another batch size between two replays of a captured
-        # step must not rewrite the weights / counts that the graph reads
-        key = ('wdev', device, B)
-        if key not in self._dev:
-            self._dev[key] = [torch.zeros(14, device=device, dtype=torch.float32), None]
-        slot = self._dev[key]
-        if slot[1] != vals:
-            if torch.cuda.is_available() and device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError('FusedMeshLoss: the term weights changed during stream capture (epoch gate or batch '
-                                   'size); call set_epoch() / run one eager step before capturing')
-            slot[0].copy_(torch.tensor(vals, dtype=torch.float32))
-            slot[1] = vals
-        return slot[0][:7], slot[0][7:]
-
     def set_epoch(self, epoch, B=None, device=None):
-        """Move the epoch gate (edge term on from NORM_EPOCH).  With a replayed hipGraph pass the captured batch size and
-        device so that the device-resident weights are refreshed in place."""
-        self.epoch = epoch
+        """As _FusedLoss.set_epoch; before the first call of this loss the coarse size, hence the counts, are unknown and
+        no slot exists: only the gate moves."""
         if self.Vc is None:
-            return
-        if B is not None and device is not None:
-            self.device_weights(B, torch.device(device))
-        else:                                       # refresh every slot that exists (all captured batch sizes / devices)
-            for key in [k for k in self._dev if k[0] == 'wdev']:
-                self.device_weights(key[2], key[1])
+            self.epoch = epoch
+        else:
+            super().set_epoch(epoch, B, device)
 
-    def topo(self, side, device):
-        from ._lib import MeshTopo
-        key = (side, device)
-        if key not in self._dev:
-            h = self._host[side]
-            t = {k: torch.as_tensor(h[k], device=device) for k in ('faces', 'vptr', 'vlist', 'perm')}
-            t['J'] = h['J'].to(device)
-            pool = h['perm'].shape[0] // self.Vc
-            assert pool * self.Vc == h['perm'].shape[0] and pool & (pool - 1) == 0
-            self._dev[key] = (t, MeshTopo(t['faces'].data_ptr(), t['vptr'].data_ptr(), t['vlist'].data_ptr(),
-                                          t['J'].data_ptr(), t['perm'].data_ptr(), h['V'], h['F'], h['NJ'], self.Vc, pool))
-        return self._dev[key][1]
+    def _coarse(self, h, device):
+        pool = h['perm'].shape[0] // self.Vc
+        assert pool * self.Vc == h['perm'].shape[0] and pool & (pool - 1) == 0
+        return torch.as_tensor(h['perm'], device=device), self.Vc, pool
 
     def __call__(self, epoch, result, handDictList, v2d_l, v2d_r, v3d_l, v3d_r, root_rel):
         """Returns (total, terms) with terms = [total, vert2d, vert3d, joint, norm, edge, coarse3d, coarse2d].
@@ -466,34 +499,21 @@ class _ManoLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_total, _g_terms):
-        grads = torch._foreach_mul(list(ctx.saved_tensors), g_total)
-        return (None, None) + tuple(grads) + (None,) * 9
+        return (None, None) + _scaled(ctx, g_total) + (None,) * 9
 
 
-class FusedManoLoss:
+class FusedManoLoss(_FusedLoss):
     """GPU drop-in for `mano_loss_GCN` (same total, terms and gradients) on the fused HIP kernel
     (csrc/rih_mano_loss.hip).  `loss_left` / `loss_right`: the ManoLoss (or GraphLoss) of each hand, whose faces, 21-joint
     regressor and up-sampling matrix w0 are held on the device.  `weights`: None, a flat dict, or the reference's nested
     cfg.LOSS_WEIGHT (see mano_loss_weights)."""
 
+    NW = 9
+
     def __init__(self, loss_left, loss_right, weights=None, img_size=256):
-        self.w = mano_loss_weights(weights)
-        self.img_size = img_size
-        self.epoch = 0
-        self._host = {}
-        for side, gl in (('left', loss_left), ('right', loss_right)):
-            faces = gl.faces.detach().cpu().numpy().astype(np.int32)
-            V = gl.J_regressor.shape[1]
-            order = np.argsort(faces.reshape(-1), kind='stable')            # entries (face*3 + corner) grouped by vertex
-            counts = np.bincount(faces.reshape(-1), minlength=V)
-            vptr = np.zeros(V + 1, np.int32)
-            vptr[1:] = np.cumsum(counts)
-            self._host[side] = dict(faces=faces, vptr=vptr, vlist=order.astype(np.int32),
-                                    J=gl.J_regressor.detach().cpu().float().contiguous(), V=V, F=faces.shape[0],
-                                    NJ=gl.J_regressor.shape[0])
+        super().__init__(mano_loss_weights(weights), loss_left, loss_right, img_size)
         w0 = getattr(loss_left, 'upsample_weight', None)
         self.upsample_target = None if w0 is None else w0.detach()
-        self._dev = {}
 
     def weights(self, B):
         """(weights[9], counts[7]): the weight of each raw sum the kernels form, and the element counts of the seven
@@ -506,45 +526,6 @@ class FusedManoLoss:
               self.w['MANO_POSE'], self.w['MANO_SHAPE']]
         w = [0.5 * a / c for a, c in zip(lw, cnt)] + [self.w['MANO_REL'] / (3.0 * B), 0.005]
         return w, [float(c) for c in cnt]
-
-    def device_weights(self, B, device):
-        """(weights[9], counts[7]) as views of one device tensor that the kernels read at run time, one slot per (device,
-        batch size), rewritten in place (outside any stream capture) only when the values change: a hipGraph captured at
-        epoch 0 picks the edge term up after `set_epoch()`."""
-        w, cnt = self.weights(B)
-        vals = tuple(w) + tuple(cnt)
-        key = ('wdev', device, B)
-        if key not in self._dev:
-            self._dev[key] = [torch.zeros(16, device=device, dtype=torch.float32), None]
-        slot = self._dev[key]
-        if slot[1] != vals:
-            if torch.cuda.is_available() and device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
-                raise RuntimeError('FusedManoLoss: the term weights changed during stream capture (epoch gate or batch '
-                                   'size); call set_epoch() / run one eager step before capturing')
-            slot[0].copy_(torch.tensor(vals, dtype=torch.float32))
-            slot[1] = vals
-        return slot[0][:9], slot[0][9:]
-
-    def set_epoch(self, epoch, B=None, device=None):
-        """Move the epoch gate (edge term on from NORM_EPOCH).  With a replayed hipGraph pass the captured batch size and
-        device so that the device-resident weights are refreshed in place (without them: every slot that exists)."""
-        self.epoch = epoch
-        if B is not None and device is not None:
-            self.device_weights(B, torch.device(device))
-        else:
-            for key in [k for k in self._dev if k[0] == 'wdev']:
-                self.device_weights(key[2], key[1])
-
-    def topo(self, side, device):
-        from ._lib import MeshTopo
-        key = (side, device)
-        if key not in self._dev:
-            h = self._host[side]
-            t = {k: torch.as_tensor(h[k], device=device) for k in ('faces', 'vptr', 'vlist')}
-            t['J'] = h['J'].to(device)
-            self._dev[key] = (t, MeshTopo(t['faces'].data_ptr(), t['vptr'].data_ptr(), t['vlist'].data_ptr(),
-                                          t['J'].data_ptr(), None, h['V'], h['F'], h['NJ'], 0, 0))
-        return self._dev[key][1]
 
     def __call__(self, epoch, result, otherInfo, v2d_l, v2d_r, v3d_l, v3d_r, root_rel, lp_gt, ls_gt, rp_gt, rs_gt,
                  img_size=None, upsample_weight=None):

@@ -161,6 +161,13 @@ def test_entry_points_refuse_bad_arguments():
         a = list(fin)
         a[i] = None
         assert lib.rih_mano_loss_final(*a) == EINVAL, i
+    # rih_mesh_loss validates the topology through the same function, and its perm, which it always reads
+    good = dict(faces=ip, vptr=ip, vlist=ip, J=p, perm=ip, V=778, F=1538, NJ=21, Vc=252, pool=4)
+    bad = [{k: None} for k in ('faces', 'vptr', 'vlist', 'J', 'perm')] + \
+        [dict(V=0), dict(V=801), dict(F=1601), dict(NJ=25), dict(pool=3)]
+    for change in bad:
+        tp = MeshTopo(*{**good, **change}.values())
+        assert lib.rih_mesh_loss(C.byref(tp), *([p] * 6), None, p, 256.0, *([p] * 5), 2, None) == EINVAL, change
 
 
 # ----------------------------------------------------------------------------- real kernels through the host-built library
