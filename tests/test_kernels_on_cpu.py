@@ -18,6 +18,7 @@ import test_gpu_elem_edges as TE     # noqa: E402
 import test_gpu_flash_edges as TF    # noqa: E402
 import test_gpu_loss as TL          # noqa: E402
 import test_gpu_mano as TMANO       # noqa: E402
+import test_gpu_mano_chunks as TMC  # noqa: E402
 import test_gpu_ops as G            # noqa: E402
 import test_gpu_rows_tiles as TRT   # noqa: E402
 import test_metrics as TMET         # noqa: E402
@@ -31,7 +32,7 @@ CPU = torch.device('cpu')
 @pytest.fixture(autouse=True)
 def _host_kernels(monkeypatch):
     from host_kernels import host_kernels_abi
-    for mod in (G, TB, TR, TL, TMANO, TRT, TF, TE):
+    for mod in (G, TB, TR, TL, TMANO, TMC, TRT, TF, TE):
         monkeypatch.setattr(mod, 'dev', lambda: CPU)
     with host_kernels_abi():
         yield
@@ -480,6 +481,45 @@ def test_mano_fused_forward_variants_and_cache():
     TMANO.test_mano_inference_without_workspace_and_two_kernel_variant(3)
     TMANO.test_mano_reads_mutated_shapedirs()
     TMANO.test_mano_matches_oracle(17)
+
+
+# ------------------------------------------------------------------------------ tests/test_gpu_mano_chunks.py on the host build
+# Sections B (17 hands: a chunk edge; six rows of the table, three of them tip centres) and C.  Section A stays on the GPU: the
+# group count of the tile-major forward is fixed at 40 in the launch code, so its chunk loop iterates from 641 hands on, and one
+# such check (training forward, backward, no-grad forward) took 82 s here.
+@pytest.mark.parametrize('row', TMC.MC.HOST_CONFIG_ROWS, ids=TMC.MC.row_id)
+def test_mano_config_across_chunk_edge_kernels(row):
+    TMC.check_config(row, 17)
+
+
+@pytest.mark.parametrize('kind', sorted(TMC.EXTREMES))
+def test_mano_pose_extremes_kernels(kind):
+    TMC.check_extremes(kind)
+
+
+def test_mano_config_table_covers_what_it_claims():
+    """The table of tests/mano_cases.py: every value of every factor at least twice; every tip centre with new_skel on and off;
+    rotation input with a tip centre and without centring; six components with a tip centre; the compared hands of the large
+    chunk-loop batches hold both ends of every chunk that group / workgroup 0 takes."""
+    MC = TMC.MC
+    rows, tips = MC.CONFIG_ROWS, (4, 8, 12, 16, 20)
+    assert len(set(rows)) == len(rows) >= 24
+    factors = [('right', 'left'), (None, 0, 9) + tips, (45, 30, 6, 'rot'), (False, True)]
+    for f, values in enumerate(factors):
+        for v in values:
+            assert sum(r[f] == v for r in rows) >= 2, (f, v)
+    for ts in ((True, True), (False, False), (True, False), (False, True)):
+        assert sum(r[4:] == ts for r in rows) >= 2, ts
+    for c in tips:
+        assert {r[3] for r in rows if r[1] == c} == {False, True}, c
+    assert any(r[2] == 'rot' and r[1] in tips for r in rows) and any(r[2] == 'rot' and r[1] is None for r in rows)
+    assert any(r[2] == 6 and r[1] in tips for r in rows)
+    assert MC.TIP_ROW_IN_CHUNK_LOOP[1] in tips and sum(r[1] in tips for r in MC.HOST_CONFIG_ROWS) >= 2
+    assert MC.compared_hands(641, MC.TILE_MAJOR) is None and MC.compared_hands(1285, MC.TILE_MAJOR) is None
+    h = set(MC.compared_hands(4097, MC.HAND_MAJOR).tolist())
+    assert {0, 15, 16, 4095, 4096} <= h and len(h) == 5 + 48
+    h = set(MC.compared_hands(8197, MC.HAND_MAJOR).tolist())
+    assert {0, 15, 16, 4095, 4096, 4111, 4112, 8191, 8192, 8196} <= h and len(h) == 10 + 48
 
 
 def test_mesh_loss_kernel():
